@@ -8,9 +8,24 @@ columns already resident in HBM.  Every step applies its OWN batch: the client m
 previous steps left (copycat_amd.workload.AtomicLongClients), so every timed step holds the stated ~10% stale CASes
 (the per-step CAS success share is reported), and the results of every step stay in HBM.
 
-Parity at full size: the oracle applies step 0's 100M rows on the host (this is also the timed CPU baseline); the
-GPU's step-0 status/value columns and its value state after step 0 must match bit for bit ("parity" in the JSON
-line; any mismatch exits non-zero).
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline figure needs and no more: it generates
+and uploads the batches, warms up, times the N steps (per-kernel HIP events included, as always), writes the last
+step's results if `--dump-outputs DIR` is given, and prints the JSON line.  Everything else below is measured or
+checked with `--full` (off by default; its fields are null in a plain line): the step-0 parity gate, the CPU
+baselines, the global-log split leg, the PCIe-inclusive steps, the c3 sub-record, c4's back-to-back per-kernel
+launches.  A plain run keeps at most 32 distinct batches resident (`--max-streams`), `--full` as many as
+`--hbm-budget-gb` holds; more steps than resident batches replay them in turn.
+
+`--dump-outputs DIR`: after the timed steps, what the last timed step's cc_apply_batch returned to its caller, as
+DIR/<name>.npy (float32 for byte columns, float64 otherwise; a 64-bit column with values past 2^53 as its exact
+32-bit halves <name>_hi32 / <name>_lo32): the per-commit status and value columns (all rows up to 2^21, else a fixed
+seeded sample of about 2^21 rows, c5 2^20, whose row numbers are rows.npy), the applied watermark, and per workload
+the value state (c2), the leading 2^19 events (c5), the commit indices and the expired bitmap (c4); under 64 MB in
+all.  The generators are seeded, so the same arguments give the same inputs and the same files.
+
+Parity at full size (`--full`): the oracle applies step 0's 100M rows on the host (this is also the timed CPU
+baseline); the GPU's step-0 status/value columns and its value state after step 0 must match bit for bit ("parity"
+in the JSON line; any mismatch exits non-zero).
 
 Multi-GPU (`--gpus N`): without WORLD_SIZE in the environment bench.py starts N ranks itself
 (torch.distributed.run, one process per GPU, RCCL) before touching any GPU.  Rank r applies its share of ONE global
@@ -91,6 +106,47 @@ def window_marker():
     charges to the timed steps exactly the kernels that start between the two (no set-up launch is counted)."""
     if WINDOW_MARKERS:
         torch.cuda._sleep(1)
+
+
+DUMP_ROWS = 1 << 21  # --dump-outputs: rows kept of a per-commit result column (status f32 + rows f64 + value f64, or its
+# two f64 halves: 58 MB at the most; c5 keeps 2^20 rows, 29 MB, beside 23 MB of events)
+PLAIN_STREAMS = 32  # distinct resident batches of a plain run (each costs ~0.4 s of set-up: generation + upload)
+
+
+def dump_rows(n, dev, draws=DUMP_ROWS):
+    """The rows of an n-row result column that --dump-outputs keeps: None (all of them) up to `draws`, else a fixed
+    seeded sample (`draws` draws: distinct, ascending) as a device index tensor."""
+    if n <= draws:
+        return None
+    rows = np.unique(np.random.default_rng(0xD0C2).integers(0, n, draws))
+    return torch.from_numpy(rows).to(dev)
+
+
+def dump_col(t, rows):
+    return (t if rows is None else t[rows]).cpu().numpy()
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy, float32 for byte-wide columns and float64 for the rest (the
+    64-bit columns are written as signed integers; one that holds a value outside float64's exact integer range, as
+    c3's random map values do, goes out as its two 32-bit halves, <name>_hi32 and <name>_lo32, so every file is exact)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.atleast_1d(np.asarray(a))
+        if a.dtype == np.uint64:
+            a = a.view(np.int64)
+        if a.dtype == np.int64 and a.size and max(int(a.max()), -int(a.min())) >= 1 << 53:
+            np.save(os.path.join(dirname, name + "_hi32.npy"), (a >> 32).astype(np.float64))
+            np.save(os.path.join(dirname, name + "_lo32.npy"), (a & 0xFFFFFFFF).astype(np.float64))
+            continue
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64))
+
+
+def resident_streams(args, total_steps, bytes_per_stream):
+    """Distinct per-step batches kept in HBM: one per step up to --hbm-budget-gb, and up to --max-streams (a plain
+    run: PLAIN_STREAMS; --full: no further limit).  More steps than that replay the resident batches in turn."""
+    cap = args.max_streams or (total_steps if args.full else PLAIN_STREAMS)
+    return max(1, min(total_steps, cap, int(args.hbm_budget_gb * 1e9 // bytes_per_stream)))
 
 
 def trace_name(marker, workload):
@@ -334,28 +390,15 @@ def run_c4(args, dev, rank, world, dist):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # Per-kernel launch durations: each kernel alone, back to back over the resident input sets, between one event
-    # pair (an event pair around every ~15 us launch adds its own few us).  k_quorum moves 88% of the algorithmic
-    # bytes (64 B/group vs 8.125 B/session): it is the roofline kernel; k_expire is launch-latency bound (8.5 MB).
-    reps = 64
-    e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-    e0.record(stream)
-    for k in range(reps):
-        d_match, d_ts, d_ci, d_last = sets[k % nsets]
-        quorum_commit(d_match, d_ts, d_ci, d_out, stream=stream)
-    e1.record(stream)
-    for k in range(reps):
-        d_match, d_ts, d_ci, d_last = sets[k % nsets]
-        expire_sweep(d_last, now, timeout, d_bm, d_cnt, stream=stream)
-    e2.record(stream)
-    torch.cuda.synchronize(dev)
-    q_ms, x_ms = e0.elapsed_time(e1) / reps, e1.elapsed_time(e2) / reps
+    if args.dump_outputs and rank == 0:  # the last timed step's outputs (before anything below launches again)
+        bits = np.unpackbits(d_bm.cpu().numpy().view(np.uint8), bitorder="little")[:S]
+        dump_outputs(args.dump_outputs, {"commit_index": d_out.cpu().numpy(), "expired_bitmap": bits,
+                                         "expired_count": d_cnt.cpu().numpy()})
     step_q_ms = sum(e[0].elapsed_time(e[1]) for e in ev) / args.steps
     step_x_ms = sum(e[1].elapsed_time(e[2]) for e in ev) / args.steps
-    q_gbps = 64 * G / (q_ms * 1e-3) / 1e9
-    x_gbps = 8.125 * S / (x_ms * 1e-3) / 1e9
-    dom = "k_quorum"
-    ach = q_gbps
+    kernels = None
+    if args.full:
+        kernels = c4_kernel_launches(sets, nsets, now, timeout, d_out, d_bm, d_cnt, stream, dev, G, S)
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle.oracle_py import expire_sweep as ox
@@ -393,14 +436,8 @@ def run_c4(args, dev, rank, world, dist):
                                                                 "WRITE_SIZE, profiles/traffic_latest.json)",
                          "alg_gb_per_step": round((64 * G + 8.125 * S) / 1e9, 4),
                          "bytes_per_unit": {"group": 64, "session": 8.125},
-                         "dominant_kernel": {"kernel": dom, "trace_name": "k_quorum<5>", "achieved": round(ach, 1),
-                                             "frac": round(ach / HBM_PEAK_GBPS, 4), "avg_launch_ms": round(q_ms, 5),
-                                             "traffic": pmc_traffic("k_quorum", "c4"), "traffic_unit": "GB per launch",
-                                             "alg_gb_per_launch": round(64 * G / 1e9, 4)},
-                         "timing": f"{reps} back-to-back launches of each kernel over the resident input sets, one event pair",
-                         "per_kernel_ms": {"k_quorum": round(q_ms, 5), "k_expire": round(x_ms, 5)},
                          "per_step_event_ms": {"k_quorum": round(step_q_ms, 5), "k_expire": round(step_x_ms, 5)},
-                         "per_kernel_gbps": {"k_quorum": round(q_gbps, 1), "k_expire": round(x_gbps, 1)}},
+                         **(kernels or {"dominant_kernel": None, "per_kernel_ms": None, "per_kernel_gbps": None})},
             "parity": parity, "cpu_baseline": cpu,
         }
         print(json.dumps(out), flush=True)
@@ -410,6 +447,36 @@ def run_c4(args, dev, rank, world, dist):
                                or parity["expired"] != parity["expired_ref"]):
         sys.stderr.write(f"PARITY FAILURE: {parity}\n")
         sys.exit(3)
+
+
+def c4_kernel_launches(sets, nsets, now, timeout, d_out, d_bm, d_cnt, stream, dev, G, S, reps=64):
+    """c4 per-kernel launch durations (--full): each kernel alone, back to back over the resident input sets, between
+    one event pair (an event pair around every ~15 us launch adds its own few us).  k_quorum moves 88% of the
+    algorithmic bytes (64 B/group vs 8.125 B/session): it is the roofline kernel; k_expire is launch-latency bound
+    (8.5 MB).  Returns the roofline sub-fields."""
+    from copycat_amd.engine import expire_sweep, quorum_commit
+
+    e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+    e0.record(stream)
+    for k in range(reps):
+        d_match, d_ts, d_ci, d_last = sets[k % nsets]
+        quorum_commit(d_match, d_ts, d_ci, d_out, stream=stream)
+    e1.record(stream)
+    for k in range(reps):
+        d_match, d_ts, d_ci, d_last = sets[k % nsets]
+        expire_sweep(d_last, now, timeout, d_bm, d_cnt, stream=stream)
+    e2.record(stream)
+    torch.cuda.synchronize(dev)
+    q_ms, x_ms = e0.elapsed_time(e1) / reps, e1.elapsed_time(e2) / reps
+    q_gbps = 64 * G / (q_ms * 1e-3) / 1e9
+    x_gbps = 8.125 * S / (x_ms * 1e-3) / 1e9
+    return {"dominant_kernel": {"kernel": "k_quorum", "trace_name": "k_quorum<5>", "achieved": round(q_gbps, 1),
+                                "frac": round(q_gbps / HBM_PEAK_GBPS, 4), "avg_launch_ms": round(q_ms, 5),
+                                "traffic": pmc_traffic("k_quorum", "c4"), "traffic_unit": "GB per launch",
+                                "alg_gb_per_launch": round(64 * G / 1e9, 4)},
+            "timing": f"{reps} back-to-back launches of each kernel over the resident input sets, one event pair",
+            "per_kernel_ms": {"k_quorum": round(q_ms, 5), "k_expire": round(x_ms, 5)},
+            "per_kernel_gbps": {"k_quorum": round(q_gbps, 1), "k_expire": round(x_gbps, 1)}}
 
 
 def per_target(ev, keys=("pos", "target", "code", "tag", "payload", "src")):
@@ -435,7 +502,7 @@ def run_c5(args, dev, rank, world, dist):
     else:  # resources created in turn (a lock, an election, a group, ...): instance r's resource has type r % 3
         types = np.resize(kinds, R)
     total_steps = args.warmup + args.steps
-    nstreams = max(1, min(total_steps, int(args.hbm_budget_gb * 1e9 // (n * 54))))
+    nstreams = resident_streams(args, total_steps, n * 54)
     flags = abi.CC_CFG_TIMERS_DEFERRED
     t_gen = time.time()
     # Session expiry: S_glob client sessions; rank r holds the keep-alives of sessions
@@ -559,6 +626,14 @@ def run_c5(args, dev, rank, world, dist):
         parity = c5_parity(parity_ref, status, value, evs, abi)
     prof = E.profile_read() if not args.no_profile else {}
     n_events = int(evs.count.item())
+    if args.dump_outputs and rank == 0:  # the last timed step's results and its leading events
+        rows, m = dump_rows(n, dev, 1 << 20), min(n_events, 1 << 19)
+        out = {"status": dump_col(status, rows), "value": dump_col(value, rows), "event_count": n_events,
+               "applied_index": wm_local.cpu().numpy()}
+        out.update({"event_" + k: getattr(evs, k)[:m].cpu().numpy() for k in ("pos", "target", "code", "tag", "payload", "src")})
+        if rows is not None:
+            out["rows"] = rows.cpu().numpy()
+        dump_outputs(args.dump_outputs, out)
     ms_per_step = elapsed * 1e3 / args.steps
     roofline = roofline_step(prof, "c5", n, args.steps, ms_per_step, B_OP_C5)
     if rank == 0:
@@ -743,7 +818,7 @@ def run_c2(args, dev, rank, world, dist):
     cols = ("index", "inst", "op", "flags", "a", "b")
     total_steps = args.warmup + args.steps
     per_stream = n * (30 + 9)  # device bytes per step: columns + results
-    nstreams = max(1, min(total_steps, int(args.hbm_budget_gb * 1e9 // per_stream)))
+    nstreams = resident_streams(args, total_steps, per_stream)
     t_gen = time.time()
     clients = AtomicLongClients(resources=R, seed=SEED_C2, rank=rank, world=world, threads=cpu_threads())
     host = Batch(n)
@@ -787,8 +862,18 @@ def run_c2(args, dev, rank, world, dist):
     wm_local = torch.zeros(1, dtype=torch.int64, device=dev)
     wm_all = torch.zeros(world, dtype=torch.int64, device=dev)
 
+    # step 0's results are the parity gate's, read after the timed steps: with more steps than resident batches, the
+    # replays of batch 0 write into a buffer of their own and leave them as step 0 wrote them
+    replay0 = None
+    if parity_ref is not None and total_steps > nstreams:
+        replay0 = (torch.full((n,), RESULT_SENTINEL, dtype=torch.uint8, device=dev),
+                   torch.full((n,), -1, dtype=torch.int64, device=dev))
+
+    def results_of(k):
+        return replay0 if replay0 is not None and k >= nstreams and k % nstreams == 0 else results[k % nstreams]
+
     def step(k):
-        st, va = results[k % nstreams]
+        st, va = results_of(k)
         E.apply(streams[k % nstreams], st, va, stream=stream)
         E.applied_index_async(wm_local, stream=stream)
         if dist is not None:  # applied-index watermark exchange (RCCL all-gather over xGMI)
@@ -830,10 +915,20 @@ def run_c2(args, dev, rank, world, dist):
     if watermarks != wm_expect:
         sys.stderr.write(f"watermark mismatch: all-gathered {watermarks}, expected {wm_expect}\n")
         sys.exit(4)
-    # CAS success share of every timed step (the stated ~0.9 of the client model)
+    if args.dump_outputs and rank == 0:  # the last timed step's results and the value state it left
+        rows = dump_rows(n, dev)
+        st, va = results_of(total_steps - 1)
+        tag, val, cur = E.value_state()
+        out = {"status": dump_col(st, rows), "value": dump_col(va, rows), "state_tag": tag, "state_value": val,
+               "state_current": cur, "applied_index": wm_local.cpu().numpy()}
+        if rows is not None:
+            out["rows"] = rows.cpu().numpy()
+        dump_outputs(args.dump_outputs, out)
+        del rows
+    # CAS success share of the timed steps whose results are still resident (the stated ~0.9 of the client model)
     shares = []
-    for k in range(args.warmup, total_steps):
-        db, (st, va) = streams[k % nstreams], results[k % nstreams]
+    for k in range(max(args.warmup, total_steps - nstreams), total_steps):
+        db, (st, va) = streams[k % nstreams], results_of(k)
         cas = db.cols["op"] == abi.CC_OP_VALUE_CAS
         shares.append(float(((va == 1) & cas).sum().item()) / max(1, int(cas.sum().item())))
     parity = None
@@ -875,7 +970,7 @@ def run_c2(args, dev, rank, world, dist):
     c3_bad = False
     if rank == 0 and world == 1 and not args.no_c3:
         # the c3 line inside the default run (an extra key, never `value`): the c2 batches leave HBM first
-        del streams, results, E
+        del streams, results, replay0, E
         torch.cuda.synchronize(dev)
         torch.cuda.empty_cache()
         out["c3"], c3_bad = c3_subrecord(args, dev)
@@ -900,6 +995,7 @@ def c3_subrecord(args, dev):
 
     a = _ap.Namespace(**vars(args))
     a.cv_rate = a.clear_rate = a.null_rate = a.delete_rate = 0.0
+    a.dump_outputs = None  # (the files are the c2 line's)
     a.pairs, a.zipf, a.sub_batch, a.cpu_sample = 1 << 20, 0.99, 0, 20_000_000
     t = time.time()
     out, bad = measure_c3(a, dev, 0, 1, None, 1_000_000_000, 3, 1, 4096)
@@ -1122,6 +1218,13 @@ def measure_c3(args, dev, rank, world, dist, n, steps, warmup, R):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     prof = E.profile_read() if not args.no_profile else {}
+    if getattr(args, "dump_outputs", None) and rank == 0:  # the last timed step's results
+        rows = dump_rows(n, dev)
+        dumped = {"status": dump_col(status, rows), "value": dump_col(value, rows), "applied_index": wm_local.cpu().numpy()}
+        if rows is not None:
+            dumped["rows"] = rows.cpu().numpy()
+        dump_outputs(args.dump_outputs, dumped)
+        del rows
     ms_per_step = elapsed * 1e3 / steps
     variant = "b" if args.null_rate or args.delete_rate else ("w" if args.cv_rate or args.clear_rate else "")
     roofline = roofline_step(prof, "c3" + variant, n, steps, ms_per_step, B_OP_C3)
@@ -1241,6 +1344,16 @@ def main():
     ap.add_argument("--delete-rate", type=float, default=0.0, help="c3 barrier variant: share of Delete rows")
     ap.add_argument("--sub-batch", type=int, default=0)
     ap.add_argument("--cpu-sample", type=int, default=0, help="c3: 20M, c5: 10M (c2 uses step 0's rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the step-0 parity gate against "
+                         "the oracle, the CPU baselines, c2's global-log split leg, PCIe-inclusive steps and c3 "
+                         "sub-record, c4's per-kernel launches (the --no-* options below take single legs out again)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last timed step's results to DIR/<name>.npy (float32 / float64; "
+                         "a fixed seeded sample of the per-commit columns, under 64 MB in all)")
+    ap.add_argument("--max-streams", type=int, default=0,
+                    help=f"c2, c5: distinct per-step batches kept resident (default: {PLAIN_STREAMS}; with --full as many as "
+                         f"--hbm-budget-gb holds); more steps than that replay them in turn")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true",
                     help="skip the oracle parity check of step 0 (c2, c5: all rows; c3: the first --cpu-sample rows; "
@@ -1262,6 +1375,8 @@ def main():
     args = ap.parse_args()
     global WINDOW_MARKERS
     WINDOW_MARKERS = args.window_markers
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_parity = args.no_cpu_baseline = args.no_split = args.no_e2e = args.no_c3 = True
 
     rc = launch_ranks(args)
     if rc is not None:

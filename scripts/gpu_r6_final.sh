@@ -11,7 +11,7 @@ tail -1 $OUT/pytest_gpu.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -5 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
 T0=$(date +%s)
-timeout -k 10 580 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.log 2>&1 || { tail -5 $OUT/bench_default.log; exit 1; }
+timeout -k 10 580 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.log 2>&1 || { tail -5 $OUT/bench_default.log; exit 1; }
 echo "default bench wall $(( $(date +%s) - T0 )) s"
 python3 -c "
 import json; d=json.loads(open('$OUT/bench_default.log').read().strip().splitlines()[-1]); c=d['c3']

@@ -1,6 +1,6 @@
 """GPU parity at (near) bench scale — the c2 / c3 / c5 streams at sizes where the bench's kernels run their full grids.
 
-c2 (100M rows) is checked in full by bench.py itself on every run (the "parity" field: step 0's 100M rows against
+c2 (100M rows) is checked in full by bench.py itself on every --full run (the "parity" field: step 0's 100M rows against
 the oracle, bit for bit); here:
   * c3: 20M rows of the Zipf(0.99) DistributedMap stream over 4,096 maps and 1,048,576 (map, key) pairs — every
     row's status/value, the applied index, and the final entries of a sample of maps (incl. the hottest);
