@@ -326,10 +326,10 @@ constexpr uint32_t kErrTime = 8u;  // the time column decreased inside a batch
 constexpr uint32_t kErrMapOrder = 16u;  // containsValue's HashMap iteration order is undetermined (map_wide.hip)
 constexpr uint32_t kErrMapSize = 32u;   // a map's tracked size differs from its table at a barrier (internal check)
 constexpr uint32_t kErrHandleHash = 64u;  // a HANDLE map key whose String.hashCode was never registered (cc_handle_hashes)
-constexpr uint32_t kErrSmallFlag = 256u;
-constexpr uint32_t kErrCoordFull = 512u;
-constexpr uint32_t kErrSpan = 1024u;      // a sub-batch with map events spans 2^32 log indices (the host cuts them first)  // a coordination collection (lock queue, listeners, members, queue) is full  // (CC_DIAG builds) a map in the small-map window without its snapshot flag
 constexpr uint32_t kErrCvKey = 128u;     // in-stream containsValue: an event past a 2^40-index span (internal check)
+constexpr uint32_t kErrSmallFlag = 256u;  // (CC_DIAG builds) a map in the small-map window without its snapshot flag
+constexpr uint32_t kErrCoordFull = 512u;  // a coordination collection (lock queue, listeners, members, queue) is full
+constexpr uint32_t kErrSpan = 1024u;      // a sub-batch with map events spans 2^32 log indices (the host cuts them first)
 
 // java.util.HashMap placement of a map key: hash(key) = h ^ (h >>> 16), h = key.hashCode() -- Long (int)(v ^ v >>> 32),
 // Integer v, Boolean 1231 / 1237, String (HANDLE) its registered String.hashCode (hh: sorted handles + hashes);

@@ -552,8 +552,12 @@ extern "C" int cc_engine_create(const cc_config* cfg, cc_engine** out) {
   if ((he = hipMemset(e->d_sb_kind, 0, e->sb)) != hipSuccess) return fail("memset", he);
   if ((he = hipMemset(e->d_clock, 0, sizeof(uint64_t))) != hipSuccess) return fail("memset", he);
   if ((he = hipMemset(e->d_last_index, 0, sizeof(uint64_t))) != hipSuccess) return fail("memset", he);
+  // (never read before an instance is opened / an entry is bound, but snapshot sections: no heap leftovers in them)
+  if ((he = hipMemset(e->d_inst_id, 0, sizeof(uint64_t) * cfg->max_instances)) != hipSuccess) return fail("memset", he);
   e->sb_kind.assign(e->sb, 0);
   if (e->map_bits) {  // word 0 = empty entry
+    if ((he = hipMemset(e->d_tbl_key, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return fail("memset", he);
+    if ((he = hipMemset(e->d_tbl_val, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return fail("memset", he);
     if ((he = hipMemset(e->d_tbl_word, 0, sizeof(uint32_t) * e->map_entries)) != hipSuccess) return fail("memset", he);
     if ((he = hipMemset(e->d_tbl_ci, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return fail("memset", he);
     if ((he = hipMemset(e->d_tbl_ins, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return fail("memset", he);
@@ -2853,7 +2857,10 @@ static std::vector<Section> snap_sections(cc_engine* e) {
 
 // ---- the prefix apply's checkpoint (host_path.hip cc_apply_batch_host_prefix) -------------------------------------
 // The device sections of a snapshot (the state every batch apply may write), the applied index and the leak log's
-// count, copied device to device into one engine-owned buffer; the host fields a batch moves beside them.
+// count, copied device to device into one engine-owned buffer; the host fields a batch moves beside them.  The leak
+// log's records are not a section: ckpt_save drains the log first, so the saved count is 0, the saved host lists hold
+// every record, and whatever a rolled-back attempt drained, reallocated (ensure_leak) or wrote into d_leak is dropped
+// by restoring that count and those lists.
 static std::vector<Section> ckpt_sections(cc_engine* e) {
   std::vector<Section> v;
   for (const Section& x : snap_sections(e))
@@ -2866,6 +2873,7 @@ static std::vector<Section> ckpt_sections(cc_engine* e) {
 int cc::ckpt_save(cc_engine* e) {
   int rc = quiesce(e);
   if (rc) return rc;
+  if ((rc = drain_leaks(e))) return rc;  // the previous batches' records live in e->leaks from here on (count 0)
   const auto secs = ckpt_sections(e);
   uint64_t need = 0;
   for (const Section& x : secs) need += (x.bytes + 255) & ~255ull;

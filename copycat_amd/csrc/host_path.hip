@@ -187,9 +187,12 @@ extern "C" int cc_apply_batch_host_events(cc_engine* e, const cc_batch* h_cols, 
 //      and nothing else), its resource block, the clock, the applied index and the pending group timers are restored
 //      (the engine skips the entry it cannot hold, so nothing else moved) and the call stops there; if it applied
 //      (the op did not add after all), the count is read once more and the pass goes on.
-// Each row is scanned once, and a stop costs one header read: a queue that stays near coord_cap under churn costs a
-// call per stop, not a rescan of the batch.  Other fixed capacities (a full map table region, max_events) still fail
-// the call after applying it.
+// Each row is scanned once, and the collection scan itself costs one header read per stop: a queue that stays near
+// coord_cap under churn costs a call per stop, not a rescan of the batch.  On an engine with maps or with an event
+// stream every part (the single row of step 2 included) also runs under a device checkpoint (ckpt_save, engine.hip:
+// a device-to-device copy of every snapshot section into a second allocation of that size, kept until the engine is
+// destroyed), taken whether or not the part then succeeds; a full map table region or a full event stream costs
+// about log2(rows of the part) restores and re-applies on top of it (`attempt` below).
 namespace {
 
 bool adds_entry(uint8_t type, uint8_t op, uint64_t aux) {
