@@ -83,32 +83,57 @@ __device__ inline uint64_t v3_set_row(uint64_t r, uint32_t row) {
   return ((r >> 17) & 1u) ? (r | ((uint64_t)row << 18)) : r;
 }
 
-// The record -> value_walk's form (common.h value_encode: meta word, canonical compare value x, canonical new
-// value y).  tile_row0 = the batch row of the record's tile start (escaped operands are read from ca / cb there).
-__device__ inline void v3_decode(uint64_t r, const uint64_t* __restrict__ ca, const uint64_t* __restrict__ cb,
-                                 uint64_t tile_row0, uint32_t& m, uint64_t& x, uint64_t& y) {
+// The record -> the walk's form: a meta word, the canonical compare value x and the canonical new value y (cf.
+// common.h value_encode; the bits are laid out for this file's walk alone, which is its slot, so none is carried):
+//   bits 0..7   the status byte of an op that does not return the current value (CAS: OK|BOOL, unknown: UNKNOWN_OP)
+//   bit 8 W     the op writes y unconditionally: set, getAndSet -- and delete, which writes "no value"
+//   bit 9 C     compareAndSet;  bit 10 R  the op returns the current value: get, getAndSet
+//   bit 11 L    listen / unlisten: events, not applied here (flagged)
+//   bits 12..14 the compare tag
+//   bits 16..31 the slot's meta word after a write (vmeta): the new tag | has-current << 8; 0 for a delete
+// The class's part comes from two byte tables indexed by a shift: byte `cls` of kV3OpLo is the status byte, of
+// kV3OpHi the W C R L bits (0..3) and has-current after a write (4).
+constexpr uint32_t kM3W = 1u << 8, kM3C = 1u << 9, kM3R = 1u << 10, kM3L = 1u << 11;
+__host__ __device__ constexpr uint32_t v3_class_bits(uint32_t cls) {  // status | W C R L << 8 | has-current << 12
+  return cls == kC3Get   ? kM3R
+         : cls == kC3Set ? (kM3W | 0x1000u)
+         : cls == kC3Cas ? (kM3C | 0x1000u | CC_STATUS(CC_ST_OK, CC_TAG_BOOL))
+         : cls == kC3Gas ? (kM3W | kM3R | 0x1000u)
+         : cls == kC3Del ? kM3W
+         : cls == kC3Lis ? kM3L
+                         : CC_STATUS(CC_ST_UNKNOWN_OP, CC_TAG_NULL);  // kC3Unk, and 7 (never encoded)
+}
+__host__ __device__ constexpr uint64_t v3_class_table(int shift) {
+  uint64_t tb = 0;
+  for (uint32_t c = 0; c < 8; ++c) tb |= (uint64_t)((v3_class_bits(c) >> shift) & 0xFFu) << (8 * c);
+  return tb;
+}
+constexpr uint64_t kV3OpLo = v3_class_table(0), kV3OpHi = v3_class_table(8);
+
+// A record whose operands are in it (not escaped).  x is the 32-bit expected value for every class: the walk reads x
+// only under C.  y is the 46-bit payload, or expected + delta for a CAS; classes without a payload (delete among
+// them) carry 0, and a delete's new tag is 0.
+__device__ inline void v3_decode(uint64_t r, uint32_t& m, uint64_t& x, uint64_t& y) {
   const uint32_t lo = (uint32_t)r;
-  const uint32_t slot = lo & 0xFFu, cls = (lo >> 8) & 7u, ct = (lo >> 11) & 7u, nt = (lo >> 14) & 7u;
-  // class -> the walk's op bits (value_encode): get R, set W, CAS C + status OK|BOOL, getAndSet W|R, delete D,
-  // listen / unlisten L (not applied here: flagged), anything else the precomputed UNKNOWN_OP status
-  uint32_t bits = CC_STATUS(CC_ST_UNKNOWN_OP, CC_TAG_NULL);
-  bits = cls == kC3Get ? kVrR : bits;
-  bits = cls == kC3Set ? kVrW : bits;
-  bits = cls == kC3Cas ? (kVrC | CC_STATUS(CC_ST_OK, CC_TAG_BOOL)) : bits;
-  bits = cls == kC3Gas ? (kVrW | kVrR) : bits;
-  bits = cls == kC3Del ? kVrD : bits;
-  bits = cls == kC3Lis ? kVrL : bits;
-  m = bits | (nt << 13) | (slot << 16) | (ct << 24);
+  const uint32_t sh = (lo >> 5) & 0x38u;  // 8 * class
+  const uint32_t kh = (uint32_t)(kV3OpHi >> sh) & 0x1Fu;
+  // kh * 0x100100 = kh << 8 | kh << 20: W C R L to bits 8..11, has-current to bit 24
+  m = ((uint32_t)(kV3OpLo >> sh) & 0xFFu) | ((kh * 0x100100u) & 0x01000F00u) |
+      ((lo << 1) & (7u << 12)) | ((lo << 2) & (7u << 16));  // compare tag 11..13 -> 12..14, new tag 14..16 -> 16..18
+  const uint64_t e = (uint64_t)(int64_t)(int32_t)(uint32_t)(r >> 18);
+  x = e;
+  y = ((lo >> 8) & 7u) == kC3Cas ? e + (uint64_t)((int64_t)r >> (64 - kV3DeltaBits)) : (uint64_t)((int64_t)r >> 18);
+}
+// An escaped record (rare): the operands from the batch columns.  tile_row0 = the batch row of the record's tile
+// start.
+__device__ inline void v3_decode_escaped(uint64_t r, const uint64_t* __restrict__ ca, const uint64_t* __restrict__ cb,
+                                         uint64_t tile_row0, uint64_t& x, uint64_t& y) {
+  const uint32_t lo = (uint32_t)r;
+  const uint32_t cls = (lo >> 8) & 7u, ct = (lo >> 11) & 7u, nt = (lo >> 14) & 7u;
   const bool cas = cls == kC3Cas, wr = cls == kC3Set || cls == kC3Gas;
-  if ((lo >> 17) & 1u) {  // escaped (rare): the operands from the batch columns
-    const uint64_t row = tile_row0 + ((r >> 18) & (kV3Tile - 1));
-    x = cas && ct ? ca[row] : 0;
-    y = cas ? (nt ? cb[row] : 0) : (wr && nt ? ca[row] : 0);
-  } else {
-    const uint64_t e = (uint64_t)(int64_t)(int32_t)(uint32_t)(r >> 18);
-    x = cas ? e : 0;
-    y = cas ? e + (uint64_t)((int64_t)r >> (64 - kV3DeltaBits)) : (wr ? (uint64_t)((int64_t)r >> 18) : 0);
-  }
+  const uint64_t row = tile_row0 + ((r >> 18) & (kV3Tile - 1));
+  x = cas && ct ? ca[row] : 0;
+  y = cas ? (nt ? cb[row] : 0) : (wr && nt ? ca[row] : 0);
 }
 
 // ---- the packed result ----------------------------------------------------------------------------------------
@@ -308,16 +333,35 @@ __global__ __launch_bounds__(kP4T) void k_part_v4(const uint32_t* __restrict__ i
 // waves 4-15 load, decode, rank and place the next chunk (3072 records) into the other LDS buffer and store the
 // previous chunk's results.  The super-bucket's list is its run in every 8192-commit tile, in tile (= log) order.
 //
+// Per chunk the loaders (`prepare`): read the results of the chunk before the walked one out of LDS, rank their
+// records into per-wave slot counters, and arrive on the LDS counter `lbar`.  ONE loader wave (a different one each
+// chunk) waits for the twelve arrivals, turns the counters in place into placement bases (slot start + the counts
+// of the waves before, k_part_v4's wave-0 scan) and the walkers' slot starts, and posts on `lbar` again.  The other
+// eleven meanwhile do everything that does not need the bases: they pack and store the results, decode their
+// records into registers, and look up and issue the loads of the chunk after; then they wait for that post.  (The
+// scanning wave does the same work after its post.)  Every wave then places its records at base + rank.
+// A record's staging position is c + (rstart -
+// rpre) of its run: the wave holds a window of 64 runs (a lane each), pushes one flag per run boundary to the lane
+// the boundary falls on (ds_permute) and counts the flags at or below each lane (ballot + mbcnt); a window with an
+// empty run (two boundaries on one lane) or with more than 64 runs takes the per-wave search instead.
+// The workgroups of one XCD (blockIdx b and b + 8 share one) take a contiguous range of super-buckets (`s` below),
+// so the 128-byte lines two neighbouring super-buckets share at their run boundaries meet in one L2.
+//
 // LDS hazards (the chunk pipeline; cf. the k_apply_map chunk-0 race):
 //   * buffer b is placed by the loaders during iteration i-1 and walked during iteration i; the one workgroup
-//     barrier per iteration separates the two, and the walkers' in-place results in b are read back by the loaders'
-//     store_results only in iteration i+1 (after the next barrier);
-//   * wcnt[b] / pbase are rewritten by `prepare` only after the loaders' arrival barrier (loader_barrier), which every
-//     loader wave reaches after its own ranking of the same chunk; wcnt[b^1] is cleared after that arrival barrier,
-//     and was last read (placement bases of the chunk before) before the previous workgroup barrier;
-//   * rstart / rpre (the run table) are written once, before the first workgroup barrier, and never rebuilt.
+//     barrier per iteration separates the two, and the walkers' in-place results in b are read back by the loaders
+//     only in iteration i+1 (after the next barrier);
+//   * those result reads (sab[b] at the top of `prepare`) come before the wave's arrival on lbar, and no wave places
+//     into sab[b] / sm[b] before the scanning wave's post, which follows all twelve arrivals: every result is in
+//     registers before its LDS word is overwritten;
+//   * wcnt (one buffer): a wave zeroes ITS OWN row at the top of `prepare` and ranks into it (one wave's LDS accesses
+//     stay in order).  The row's other accesses are the scanning wave's (read + rewritten between the twelve arrivals
+//     and its post) and the wave's own base reads at the placement (after the post, before the workgroup barrier);
+//     the next zeroing comes after that barrier;
+//   * sstart[b] is written by the scanning wave before the workgroup barrier and read by the walkers after it;
+//   * lbar only grows: 13 per chunk (twelve arrivals + the post); each wave counts the same targets in a register;
+//   * rb0 / rpre (the run table) are written once, before the first workgroup barrier, and never rebuilt.
 constexpr int kWsPer = 4;
-constexpr uint32_t kNoPos3 = 0xFFFFFFFFu;
 // NS slots per super-bucket: 256 (1024-thread workgroups: 4 walker + 12 loader waves, 3072-record chunks, one
 // workgroup per CU) or 128 (512-thread workgroups: 2 walker + 6 loader waves, 1536-record chunks, 79 KB of LDS: two
 // workgroups per CU, so one workgroup's per-chunk loader chain -- rank, arrival barrier, placement bases, placement
@@ -339,13 +383,13 @@ struct V3A {
 __device__ inline uint32_t v3_value_walk(uint32_t m, uint64_t x, uint64_t y, uint32_t& ms, uint64_t& v, uint64_t& rv) {
   const uint32_t tag = ms & 0xFFu;
   // compareAndSet :124 (value == null && expect == null) || (value != null && value.equals(expect))
-  const bool eq = vrec_ctag(m) == tag && v == x;
-  const bool is_c = (m & kVrC) != 0, is_r = (m & kVrR) != 0, is_d = (m & kVrD) != 0;
-  const bool wr = (m & kVrW) != 0 || (is_c && eq);
-  rv = is_r ? v : ((is_c && eq) ? 1ull : 0ull);
+  const bool ceq = (m & kM3C) != 0 && ((m >> 12) & 7u) == tag && v == x;
+  const bool is_r = (m & kM3R) != 0;
+  const bool wr = (m & kM3W) != 0 || ceq;  // (a delete writes "no value": y = 0, meta 0)
+  rv = is_r ? v : (ceq ? 1ull : 0ull);
   const uint32_t st = is_r ? (tag << 4) : (m & 0xFFu);
-  ms = wr ? (vrec_ntag(m) | 0x100u) : (is_d ? 0u : ms);
-  v = wr ? y : (is_d ? 0ull : v);
+  ms = wr ? (m >> 16) : ms;
+  v = wr ? y : v;
   return st;
 }
 
@@ -361,9 +405,12 @@ __device__ inline uint32_t v3_find_run(const uint32_t* rpre, uint32_t tiles, uin
   return base + (uint32_t)(63 - __clzll((long long)b));
 }
 
-__device__ inline void v3_loader_barrier(uint32_t* ctr, uint32_t target) {
+// The loaders' LDS counter: arrive (this wave's earlier LDS accesses are done), wait (the counter reached target).
+__device__ inline void v3_loader_arrive(uint32_t* ctr) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   if (__lane_id() == 0) __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ inline void v3_loader_wait(uint32_t* ctr, uint32_t target) {
   while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < target) __builtin_amdgcn_s_sleep(1);
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
@@ -382,12 +429,13 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
 #else
   constexpr uint32_t diag = 0;
 #endif
-  constexpr int kWsLW = P::LW, kWsCh = P::CH, kAVT = P::T, kAVW = P::W, kVSlots3 = NS, kVPairs3 = P::NP;
+  constexpr int kWsLW = P::LW, kWsCh = P::CH, kAVW = P::W, kVSlots3 = NS, kVPairs3 = P::NP;
   constexpr uint32_t kL0 = P::WW * kWave;       // first loader thread
   __shared__ u64x2 sab[2][kWsCh];               // chunk buffers sorted by slot; results in place {value, status}
   __shared__ uint32_t sm[2][kWsCh];             //   meta words
-  __shared__ uint32_t wcnt[2][kWsLW][kVPairs3];  // per-loader-wave slot counts (packed u16 pairs), double-buffered
-  __shared__ uint16_t pbase[kWsLW][kVSlots3];   // per loader wave: sorted position of its first record of each slot
+  // per-loader-wave slot counts (packed u16 pairs); after the chunk's scan, in place: the sorted position of the
+  // wave's first record of each slot (a chunk holds 3072 records at most, so positions fit the u16 halves too)
+  __shared__ uint32_t wcnt[kWsLW][kVPairs3];
   __shared__ uint32_t sstart[2][kVSlots3 + 1];  // slot run starts of each buffer (+ total)
   __shared__ uint16_t rb0[kV3MaxTiles];         // start of this super-bucket's run inside tile r
   __shared__ uint32_t rpre[kV3MaxTiles + 1];    // records of this super-bucket before tile r
@@ -395,7 +443,12 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
   __shared__ uint32_t lbar;
   auto rstart = [&](uint32_t r) -> uint32_t { return r * kV3Tile + rb0[r]; };  // staging position of run r
 
-  const uint32_t s = blockIdx.x, t = threadIdx.x, w = t >> 6, l = t & 63;
+  // Workgroups b and b + 8 share an XCD (observed dispatch; speed only, any placement gives the same results):
+  // workgroup 8y + x takes super-bucket x*q + min(x, r) + y (q = grid / 8, r = grid % 8), a bijection for any grid
+  // that gives the workgroups of one XCD a contiguous range of super-buckets.
+  const uint32_t gx_ = blockIdx.x & 7u, gq_ = gridDim.x >> 3, gr_ = gridDim.x & 7u;
+  const uint32_t s = gx_ * gq_ + (gx_ < gr_ ? gx_ : gr_) + (blockIdx.x >> 3);
+  const uint32_t t = threadIdx.x, w = t >> 6, l = t & 63;
   const bool walker = t < kL0;
   const uint32_t lw = walker ? 0u : w - P::WW;
   uint32_t ms = 0;
@@ -404,8 +457,7 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
     ms = val_meta[(uint64_t)s * kVSlots3 + t];
     sv = val_v[(uint64_t)s * kVSlots3 + t];
   }
-  for (uint32_t k = t; k < (uint32_t)(2 * kWsLW * kVPairs3); k += kAVT) (&wcnt[0][0][0])[k] = 0;
-  if (t == 0) lbar = 0;
+  if (t == 0) lbar = 0;  // (wcnt: every loader wave zeroes its row before it ranks)
   {  // the super-bucket's list = its run in every tile, in tile order; thread t owns tiles TPT*t .. TPT*t + TPT-1
     uint32_t len[P::TPT], lsum = 0;
 #pragma unroll
@@ -444,7 +496,7 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
   }
   const uint32_t cnt = rpre[tiles];
   const uint32_t nch = (cnt + kWsCh - 1) / kWsCh;
-  uint32_t err = 0;
+  uint32_t err = 0, macc = 0;  // macc: OR of the meta words this thread walked
 #ifdef CC_PHASE_TIMING
   // thread 0 (walker): 0 walk, 1 wait; thread 256 (loader): 2 result store, 3 rank, 4 loader + workgroup barriers,
   // 5 clear + placement bases, 6 decode + place, 7 load issue
@@ -463,28 +515,32 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
   // loader registers: the chunk to place next (rr, g; loaded one chunk ahead), the sorted / staging positions of the
   // chunk being walked (pp, gp) and of the chunk before it (qp, gq: its results are stored during the walk)
 #define CC_J4(X) X(0) X(1) X(2) X(3)
-#define CC_DECL(J) uint32_t g##J = kNoPos3, pp##J = 0, gp##J = kNoPos3, qp##J = 0, gq##J = kNoPos3; uint64_t rr##J = 0;
+  // A record past the end of the list has the staging position dpos, one of the dummy words behind the staging area
+  // (its loads and result stores stay unconditional): a position is live iff it is below dpos0.
+  const uint32_t dpos0 = (uint32_t)dummy, dpos = dpos0 + t;
+#define CC_DECL(J) uint32_t g##J = dpos, pp##J = 0, gp##J = dpos, qp##J = 0, gq##J = dpos; uint64_t rr##J = 0;
   CC_J4(CC_DECL)
 #undef CC_DECL
-  // record c0 + lw*256 + j*64 + l of the list (log order = (loader wave, j, lane)); past the end: staging position 0.
-  // Staging position of list record c: the run r holding it gives rstart[r] + c - rpre[r]; one 64-ary search per wave
-  // and chunk finds the wave's first run, lane k then holds window run rrow + k, and rows find their runs with ballots.
+  // record c0 + lw*256 + j*64 + l of the list (log order = (loader wave, j, lane)).
+  // Staging position of list record c: the run r holding it gives c + (rstart[r] - rpre[r]).  One 64-ary search per
+  // wave and chunk finds the wave's first run; lane k then holds the end wB and the offset wD of window run rrow + k.
+  // Per 64-record group: the runs that end at or before the group's first record are counted with one ballot; every
+  // run that ends inside the group (at record crow + d, 0 < d < 64) pushes a flag to lane d, and lane l's run is the
+  // first one plus the flags on lanes 1..l.  (Lanes with nothing to push target lane 0, whose flag is not counted.
+  // The window runs that matter are non-empty -- `win` -- so no two of them push to one lane.)
 #define CC_LOAD1(J)                                                                               \
   {                                                                                               \
     const uint32_t crow = c0w + (J) * kWave, c = crow + l;                                        \
-    uint32_t gpos = 0;                                                                            \
+    uint32_t gpos = dpos;                                                                         \
     if (crow < cnt) { /* wave-uniform */                                                          \
       if (win) {                                                                                  \
-        uint32_t ri = (uint32_t)__popcll(__ballot(wB <= crow));                                   \
-        uint64_t mb = __ballot(wB > crow && wB <= crow + (kWave - 1));                            \
-        while (mb) {                                                                              \
-          const uint32_t bk = (uint32_t)__builtin_amdgcn_readlane((int)wB, __ffsll((long long)mb) - 1); \
-          ri += c >= bk ? 1u : 0u;                                                                \
-          mb &= mb - 1;                                                                           \
-        }                                                                                         \
-        const uint32_t rs_ = (uint32_t)__shfl((int)wS, (int)ri, 64);                              \
-        const uint32_t rp_ = (uint32_t)__shfl((int)wP, (int)ri, 64);                              \
-        if (c < cnt) gpos = rs_ + (c - rp_);                                                      \
+        const uint32_t ri0 = (uint32_t)__popcll(__ballot(wB <= crow));                            \
+        const uint32_t d_ = wB - crow;                                                            \
+        const uint32_t fl_ = (uint32_t)__builtin_amdgcn_ds_permute((int)((d_ - 1u < kWave - 1u ? d_ : 0u) << 2), 1); \
+        const uint64_t fm_ = __ballot(fl_ != 0) >> 1;                                             \
+        const uint32_t ri = __builtin_amdgcn_mbcnt_hi((uint32_t)(fm_ >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm_, ri0)); \
+        const uint32_t rd_ = (uint32_t)__shfl((int)wD, (int)ri, 64);                              \
+        if (c < cnt) gpos = c + rd_;                                                              \
       } else {                                                                                    \
         uint32_t r = v3_find_run(rpre, tiles, crow);                                              \
         if (c < cnt) {                                                                            \
@@ -493,29 +549,51 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
         }                                                                                         \
       }                                                                                           \
     }                                                                                             \
-    if (diag & 2u) gpos = c < cnt ? c : 0u; /* diagnostics: contiguous positions (wrong results) */ \
-    g##J = c < cnt ? gpos : kNoPos3;                                                              \
+    if (diag & 2u) gpos = c < cnt ? c : dpos; /* diagnostics: contiguous positions (wrong results) */ \
+    g##J = gpos;                                                                                  \
     rr##J = st_rec[gpos];                                                                         \
   }
 #define CC_LOAD_CHUNK(C0)                                                                         \
   {                                                                                               \
     const uint32_t c0w = (C0) + lw * (kWave * kWsPer);                                            \
-    uint32_t wB = 0xFFFFFFFFu, wS = 0, wP = 0;                                                    \
+    uint32_t wB = 0xFFFFFFFFu, wD = 0;                                                            \
     bool win = false;                                                                             \
     if (c0w < cnt) {                                                                              \
       const uint32_t rrow = v3_find_run(rpre, tiles, c0w);                                        \
       const uint32_t kr = rrow + l;                                                               \
-      wB = kr + 1 <= tiles ? rpre[kr + 1] : 0xFFFFFFFFu;                                          \
-      wS = kr < tiles ? rstart(kr) : 0u;                                                          \
-      wP = kr < tiles ? rpre[kr] : 0u;                                                            \
+      const uint32_t wP = kr < tiles ? rpre[kr] : 0xFFFFFFFFu;                                    \
+      wB = kr < tiles ? rpre[kr + 1] : 0xFFFFFFFFu;                                               \
+      wD = kr < tiles ? rstart(kr) - wP : 0u;                                                     \
       const uint32_t lastc = c0w + kWave * kWsPer - 1 < cnt ? c0w + kWave * kWsPer - 1 : cnt - 1; \
-      win = (uint32_t)__shfl((int)wB, 63, 64) > lastc;                                            \
+      /* the window reaches past the wave's last record, and none of its runs up to there is empty */ \
+      win = (uint32_t)__shfl((int)wB, 63, 64) > lastc && __ballot(wB == wP && wP <= lastc) == 0;  \
     }                                                                                             \
     CC_J4(CC_LOAD1)                                                                               \
   }
-  uint32_t bar_n = 0;  // loader-barrier arrivals expected so far
-  // rank / place the registers' chunk into buffer b (loaders only)
-  auto prepare = [&](uint32_t b) {
+  uint32_t bar_n = 0;  // the loaders' counter (lbar) after the previous chunk
+  // the results of the chunk walked before (buffer b, positions qp / gq) into registers, ahead of the placement that
+  // overwrites them; then over the records themselves at their staging positions (each record is read once, by this
+  // workgroup, a chunk earlier): one packed word per result (v3_pack_result), unconditional stores (rows past the
+  // end go to the dummy words).  A value that does not fit the word also goes to rst_value: looked for once per
+  // wave and group, so the common path has no per-lane branch.
+#define CC_RES_READ(J) const u64x2 re##J = sab[b][qp##J];
+#define CC_RES_WRITE(J)                                                             \
+  {                                                                                 \
+    const bool esc_ = !v3_fits(re##J.x, kV3ResBits) && gq##J < dpos0;               \
+    uint64_t wd_ = v3_pack_result((uint32_t)re##J.y, re##J.x, false);               \
+    if (__ballot(esc_)) { /* wave-uniform, rare */                                  \
+      if (esc_) {                                                                   \
+        wd_ = v3_pack_result((uint32_t)re##J.y, re##J.x, true);                     \
+        rst_value[gq##J] = re##J.x;                                                 \
+      }                                                                             \
+    }                                                                               \
+    st_rec[gq##J] = wd_;                                                            \
+  }
+  // One chunk's loader work: the results of chunk i-1 out of buffer b, then the registers' chunk (i+1) ranked and
+  // placed into buffer b; loader wave scan_w turns the counters into the placement bases for all.
+  auto prepare = [&](uint32_t b, uint32_t scan_w, uint32_t next_c0) {
+    CC_J4(CC_RES_READ)
+    for (uint32_t k = l; k < (uint32_t)kVPairs3; k += kWave) wcnt[lw][k] = 0;
     uint32_t rank[kWsPer], slot[kWsPer];
     const uint64_t rv4[kWsPer] = {rr0, rr1, rr2, rr3};
     const uint32_t gv[kWsPer] = {g0, g1, g2, g3};
@@ -523,91 +601,99 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
     for (int j = 0; j < kWsPer; ++j) {
       slot[j] = v3_slot(rv4[j]);
       const uint32_t sh = 16 * (slot[j] & 1);
-      rank[j] = gv[j] != kNoPos3 ? (atomicAdd(&wcnt[b][lw][slot[j] >> 1], 1u << sh) >> sh) & 0xFFFFu : 0u;
+      rank[j] = gv[j] < dpos0 ? (atomicAdd(&wcnt[lw][slot[j] >> 1], 1u << sh) >> sh) & 0xFFFFu : 0u;
     }
     WPH(3);
-    bar_n += kWsLW;
-    v3_loader_barrier(&lbar, bar_n);  // every loader wave has ranked this chunk into wcnt[b]
-    WPH(4);
-    // the other counter buffer was last read before the previous workgroup barrier: clear it for the next chunk
-    for (uint32_t k = t - kL0; k < (uint32_t)(kWsLW * kVPairs3); k += kWsLW * kWave) (&wcnt[b ^ 1][0][0])[k] = 0;
-    // this wave's placement bases: lane l owns slots SPL*l .. SPL*l + SPL-1 (counter pairs SPL/2*l ..)
-    constexpr int PPL = P::SPL / 2;
-    uint32_t acc[PPL], own[PPL];
+    v3_loader_arrive(&lbar);  // this wave has ranked the chunk, and has chunk i-1's results in registers
+    if (lw == scan_w) {       // wave-uniform
+      v3_loader_wait(&lbar, bar_n + kWsLW);  // every loader wave has arrived
+      WPH(4);
+      // lane l owns slots SPL*l .. SPL*l + SPL-1 (counter pairs PPL*l ..): the slots' totals over the waves, their
+      // exclusive scan (the slot starts), then each wave's counter replaced by start + the counts of the waves before
+      constexpr int PPL = P::SPL / 2;
+      uint32_t acc[PPL], mine = 0;
 #pragma unroll
-    for (int e = 0; e < PPL; ++e) acc[e] = own[e] = 0;
+      for (int e = 0; e < PPL; ++e) acc[e] = 0;
 #pragma unroll
-    for (int q = 0; q < kWsLW; ++q) {
+      for (int q = 0; q < kWsLW; ++q) {
+#pragma unroll
+        for (int e = 0; e < PPL; ++e) acc[e] += wcnt[q][PPL * l + e];
+      }
+#pragma unroll
+      for (int e = 0; e < PPL; ++e) mine += (acc[e] & 0xFFFFu) + (acc[e] >> 16);
+      uint32_t inc = mine;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(inc, d, 64);
+        if (l >= (uint32_t)d) inc += y;
+      }
+      uint32_t run = inc - mine;
 #pragma unroll
       for (int e = 0; e < PPL; ++e) {
-        const uint32_t cv = wcnt[b][q][PPL * l + e];
-        if ((uint32_t)q == lw) own[e] = acc[e];
-        acc[e] += cv;
+        const uint32_t k = P::SPL * l + 2 * e;
+        const uint32_t lo_ = run, hi_ = run + (acc[e] & 0xFFFFu);
+        sstart[b][k] = lo_;  // the walkers' run starts (read after the workgroup barrier)
+        sstart[b][k + 1] = hi_;
+        run = hi_ + (acc[e] >> 16);
+        acc[e] = lo_ | (hi_ << 16);
       }
-    }
-    uint32_t mine = 0;
+      if (l == 63) sstart[b][kVSlots3] = inc;
 #pragma unroll
-    for (int e = 0; e < PPL; ++e) mine += (acc[e] & 0xFFFFu) + (acc[e] >> 16);
-    uint32_t inc = mine;
+      for (int q = 0; q < kWsLW; ++q) {
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(inc, d, 64);
-      if (l >= (uint32_t)d) inc += y;
+        for (int e = 0; e < PPL; ++e) {
+          const uint32_t cv = wcnt[q][PPL * l + e];
+          wcnt[q][PPL * l + e] = acc[e];
+          acc[e] += cv;  // no carry between the halves: every sum is a position <= 3072
+        }
+      }
+      WPH(5);
+      v3_loader_arrive(&lbar);  // the post: the bases are in wcnt
     }
-    uint32_t run = inc - mine;
-#pragma unroll
-    for (int e = 0; e < PPL; ++e) {
-      const uint32_t k = P::SPL * l + 2 * e;
-      pbase[lw][k] = (uint16_t)(run + (own[e] & 0xFFFFu));
-      if (lw == 0) sstart[b][k] = run;  // the walkers' run starts (read after the workgroup barrier)
-      run += acc[e] & 0xFFFFu;
-      pbase[lw][k + 1] = (uint16_t)(run + (own[e] >> 16));
-      if (lw == 0) sstart[b][k + 1] = run;
-      run += acc[e] >> 16;
+    bar_n += kWsLW + 1;
+    CC_J4(CC_RES_WRITE)
+    WPH(2);
+#define CC_SHIFT1(J) qp##J = pp##J; gq##J = gp##J;
+    CC_J4(CC_SHIFT1)
+#undef CC_SHIFT1
+    // the decode does not need the bases: it runs while the scanning wave works
+#define CC_DEC1(J)                                                                  \
+    const bool live##J = g##J < dpos0;                                              \
+    uint32_t m##J;                                                                  \
+    uint64_t x##J, y##J;                                                            \
+    v3_decode(rr##J, m##J, x##J, y##J);                                             \
+    if (__ballot(live##J && (((uint32_t)rr##J >> 17) & 1u))) { /* wave-uniform, rare: an escaped record */ \
+      if (live##J && (((uint32_t)rr##J >> 17) & 1u))                                \
+        v3_decode_escaped(rr##J, ca, cb, lo + (uint64_t)(g##J / kV3Tile) * kV3Tile, x##J, y##J); \
     }
-    if (lw == 0 && l == 63) sstart[b][kVSlots3] = inc;
-    WPH(5);
-    // lanes read bases other lanes of this wave just wrote: LDS keeps one wave's accesses in order
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+    CC_J4(CC_DEC1)
+#undef CC_DEC1
+    WPH(6);
+    // nor do the position lookups and the loads of the chunk after: the registers' records are decoded
+#define CC_KEEP1(J) gp##J = g##J;
+    CC_J4(CC_KEEP1)
+#undef CC_KEEP1
+    CC_LOAD_CHUNK(next_c0)
+    WPH(7);
+    v3_loader_wait(&lbar, bar_n);  // the scanning wave's post (every loader wave waits, the scanning one for itself)
+    WPH(4);
+    const uint16_t* pb = reinterpret_cast<const uint16_t*>(&wcnt[lw][0]);  // u16 half k = slot k (little endian)
 #define CC_PLACE1(J)                                                                \
     {                                                                               \
-      pp##J = 0;                                                                    \
-      gp##J = g##J;                                                                 \
-      if (g##J != kNoPos3) {                                                        \
-        uint32_t m_;                                                                \
-        uint64_t x_, y_;                                                            \
-        v3_decode(rr##J, ca, cb, lo + (uint64_t)(g##J / kV3Tile) * kV3Tile, m_, x_, y_); \
-        pp##J = pbase[lw][slot[J]] + rank[J];                                       \
-        sm[b][pp##J] = m_;                                                          \
-        sab[b][pp##J] = u64x2{x_, y_};                                              \
+      pp##J = live##J ? pb[slot[J]] + rank[J] : 0u;                                 \
+      if (live##J) {                                                                \
+        sm[b][pp##J] = m##J;                                                        \
+        sab[b][pp##J] = u64x2{x##J, y##J};                                          \
       }                                                                             \
     }
     CC_J4(CC_PLACE1)
 #undef CC_PLACE1
     WPH(6);
   };
-  // the previous chunk's results (buffer b) back to the records' staging positions, over the records themselves
-  // (each record is read once, by this workgroup, a chunk earlier): one packed word per result (v3_pack_result),
-  // unconditional stores (rows past the end go to the dummy words); an escaped value also goes to rst_value
-  auto store_results = [&](uint32_t b) {
-#define CC_STORE1(J)                                                                \
-    {                                                                               \
-      const uint64_t gx = gq##J != kNoPos3 ? (uint64_t)gq##J : dummy + t;           \
-      const u64x2 r_ = sab[b][qp##J];                                               \
-      const bool esc_ = !v3_fits(r_.x, kV3ResBits);                                 \
-      st_rec[gx] = v3_pack_result((uint32_t)r_.y, r_.x, esc_);                      \
-      if (esc_ && gq##J != kNoPos3) rst_value[gx] = r_.x;                            \
-    }
-    CC_J4(CC_STORE1)
-#undef CC_STORE1
-  };
 
   if (!walker) {
     CC_LOAD_CHUNK(0)
-    prepare(0);
-    CC_LOAD_CHUNK(kWsCh)
+    prepare(0, 0, kWsCh);
   }
   lds_barrier();
   for (uint32_t i = 0; i < nch; ++i) {
@@ -621,7 +707,7 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
         auto fetch = [&](uint32_t k0, uint32_t (&mm)[4], u64x2 (&xx)[4]) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const uint32_t pq = start + k0 + q <= last ? start + k0 + q : last;
+            const uint32_t pq = min(start + k0 + q, last);
             mm[q] = sm[b][pq];
             xx[q] = sab[b][pq];
           }
@@ -632,7 +718,7 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
             if (k0 + q < run) {
               uint64_t rv;
               const uint32_t stt = v3_value_walk(mm[q], xx[q].x, xx[q].y, ms, sv, rv);
-              if (mm[q] & kVrL) err |= kErrUnsupported;
+              macc |= mm[q];
               // the result over the record, one 16-byte LDS write: with 2 reads + 1 write per record, a group of 4
               // records' reads plus the previous group's writes stay within the 15 outstanding LDS operations a
               // wave can wait on precisely (two writes per record overflowed it and serialised the pipeline)
@@ -650,24 +736,25 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
         }
       }
     } else {
-      store_results(b ^ 1);  // chunk i-1 (i = 0: the dummy rows)
-      WPH(2);
-#define CC_SHIFT1(J) qp##J = pp##J; gq##J = gp##J;
-      CC_J4(CC_SHIFT1)
-#undef CC_SHIFT1
-      prepare(b ^ 1);        // chunk i+1 (past the end: no live records)
-      CC_LOAD_CHUNK((i + 2) * kWsCh)
-      WPH(7);
+      // chunk i-1's results (i = 0: the dummy rows), chunk i+1's placement (past the end: no live records)
+      prepare(b ^ 1, (i + 1) % (uint32_t)kWsLW, (i + 2) * kWsCh);
     }
     if (walker) WPH(0);
     lds_barrier();  // buffer hand-over: b walked (results in place), b^1 placed
     WPH(walker ? 1 : 4);
   }
-  if (!walker && nch) store_results((nch - 1) & 1);  // the last chunk (qp / gq since its walk)
+  if (!walker && nch) {  // the last chunk's results (qp / gq since its walk)
+    const uint32_t b = (nch - 1) & 1;
+    CC_J4(CC_RES_READ)
+    CC_J4(CC_RES_WRITE)
+  }
+  if (macc & kM3L) err |= kErrUnsupported;  // a listen / unlisten record among the walked ones
 #ifdef CC_PHASE_TIMING
   if (t == 0 || t == kL0)
     for (int q = 0; q < kPhases; ++q) atomicAdd(&g_ph_v3a[q], (unsigned long long)wph[q]);
 #endif
+#undef CC_RES_READ
+#undef CC_RES_WRITE
 #undef CC_LOAD_CHUNK
 #undef CC_LOAD1
 #undef CC_J4
@@ -785,7 +872,8 @@ int launch_part_v3(const PartArgs& a, uint32_t tiles, hipStream_t st) {
 }
 
 int launch_apply_value_v3(const ValueArgs& a, hipStream_t st) {
-  if (a.tiles > (uint32_t)kV3MaxTiles) return -1;
+  // (the kernel keeps staging positions, the dummy words' among them, in 32 bits)
+  if (a.tiles > (uint32_t)kV3MaxTiles || a.dummy + V3A<256>::T > 0xFFFFFFFFull) return -1;
   hipLaunchKernelGGL(k_apply_value_v3<256>, dim3(a.sb_val), dim3(V3A<256>::T), 0, st,
                      reinterpret_cast<uint64_t*>(a.st_ab), a.ca, a.cb, a.lo, a.ttab, a.tiles, a.sb, a.val_meta, a.val_v,
                      a.rst_value, a.dummy, a.err);
