@@ -259,6 +259,18 @@ struct LeakRec {
 constexpr uint32_t kCoordCapDefault = 64;
 constexpr uint32_t kCoordCapMax = 65536;
 __host__ __device__ inline size_t coord_block(uint32_t cap) { return sizeof(CoordHdr) + (size_t)cap * sizeof(CoordEnt); }
+// a commit that can add an entry to its resource's coordination block (the only rows that can overflow one: the
+// prefix applies cut a batch at them, host_path.hip on the host's columns, prefix_scan.hip on device columns)
+__host__ __device__ inline bool adds_entry(uint8_t type, uint8_t op, uint64_t aux) {
+  switch (type) {
+    case CC_RES_LOCK: return op == CC_OP_LOCK_LOCK && aux != 0;  // tryLock() (timeout 0) never queues
+    case CC_RES_ELECTION: return op == CC_OP_ELECT_LISTEN;
+    case CC_RES_GROUP: return op == CC_OP_GROUP_JOIN;
+    case CC_RES_VALUE: return op == CC_OP_VALUE_LISTEN;
+    case CC_RES_QUEUE: return op == CC_OP_QUEUE_ADD || op == CC_OP_QUEUE_OFFER;
+    default: return false;
+  }
+}
 // One staged record of the extended partition (map, set, multimap, coordination and value-event commits), one
 // 48-byte record per staging position: a bucket's run is then one contiguous span per chunk (its cache lines are
 // written whole while they sit in L2) instead of five column spans.  Value commits for k_apply_value keep the

@@ -103,7 +103,8 @@ static void free_all(cc_engine* e) {
                   e->d_cvq,      e->d_cvq_n,    e->d_isc,     e->d_isc2,     e->d_mfirst,     e->d_maynull, e->d_cv_rtemp,
                   e->d_cvset,    e->d_cvcnt,    e->d_cvev_key, e->d_cvev_key2, e->d_cvev_val, e->d_cvev_val2, e->d_cvev_ctl,
                   e->d_cvseg,    e->d_cvtemp,   e->d_clrq,    e->d_clrq_n,   e->d_clr_keys,   e->d_clr_keys2, e->d_clr_off,
-                  e->d_clr_base, e->d_clr_eend, e->d_clr_temp, e->d_tbl_ep, e->d_clr_scan, e->d_clr_stemp, e->d_clr_btab, e->d_sm_cseg, e->d_cvbloom};
+                  e->d_clr_base, e->d_clr_eend, e->d_clr_temp, e->d_tbl_ep, e->d_clr_scan, e->d_clr_stemp, e->d_clr_btab, e->d_sm_cseg, e->d_cvbloom,
+                  e->d_px,       e->d_px_bcnt,  e->d_px_evn};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void*& p : e->hw_buf)
@@ -2897,6 +2898,21 @@ int cc::ckpt_save(cc_engine* e) {
   e->ckpt.gtimers = e->gtimers;
   e->ckpt.gtimer_seq = e->gtimer_seq;
   e->ckpt.leaks = e->leaks;
+  return CC_OK;
+}
+
+// The buffer ckpt_save copies into, allocated ahead of the first row of a prefix apply (a call that cannot have its
+// checkpoint fails before it applies anything).  The slack covers the leak log's counter, which becomes a section
+// when a batch first allocates the log.
+int cc::ckpt_reserve(cc_engine* e) {
+  uint64_t need = 1024;
+  for (const Section& x : ckpt_sections(e)) need += (x.bytes + 255) & ~255ull;
+  if (need <= e->ckpt_bytes) return CC_OK;
+  if (e->d_ckpt) HIPCHECK(hipFree(e->d_ckpt));
+  e->d_ckpt = nullptr;
+  e->ckpt_bytes = 0;
+  HIPCHECK(hipMalloc(&e->d_ckpt, need));
+  e->ckpt_bytes = need;
   return CC_OK;
 }
 

@@ -593,6 +593,34 @@ int launch_ev_shift(uint32_t* pos, uint64_t n, uint32_t by, hipStream_t st);
 constexpr uint64_t kEvChunk = 8192;  // arena events per bucketing workgroup (events.hip)
 inline uint64_t ev_chunk_cap(uint64_t arena_cap) { return (arena_cap + kEvChunk - 1) / kEvChunk; }
 
+// The stop scan of cc_apply_batch_prefix (prefix_scan.hip): the first row of [lo, hi) that adds an entry to a
+// coordination block its resource's count and the adding rows before it have filled.
+constexpr uint32_t kPxBlock = 256;       // threads of a scan workgroup = rows of one ranked tile
+constexpr uint32_t kPxMaxBlocks = 1024;  // row chunks of the rank pass (a chunk is a multiple of kPxBlock rows)
+constexpr uint32_t kPxGroup = 4096;      // listed resources ranked per pass (LDS counters)
+struct PxArgs {
+  const uint32_t* inst;  // device columns (aux may be null)
+  const uint8_t* op;
+  const uint64_t* aux;
+  uint64_t lo, hi;
+  const uint32_t* inst_res;
+  const uint8_t* res_type;
+  uint32_t max_inst, slots;
+  const uint8_t* coord;
+  uint32_t coord_cap;
+  uint32_t* cnt;             // [slots] adding rows per resource; after the pick: list position + 1 (0: not listed)
+  uint32_t* list_res;        // [slots] resources that would pass coord_cap ...
+  uint32_t* list_room;       // [slots] ... and the entries each still holds
+  uint32_t* list_n;
+  uint32_t* min_tb;          // the earliest chunk that holds a listed resource's stop row (~0: none yet)
+  unsigned long long* stop;  // the stop row (~0: none)
+  uint32_t* bcnt;            // [chunks][listed resources of the group] adding rows (rank pass)
+  uint32_t* tblk;            // [kPxGroup] the chunk holding each listed resource's stop row ...
+  uint32_t* tbase;           // [kPxGroup] ... and its adding rows before that chunk
+};
+int launch_px_count(const PxArgs& a, hipStream_t st);  // passes 1 and 2: the list and its length
+int launch_px_rank(const PxArgs& a, uint32_t g0, uint32_t mg, uint32_t nblk, uint64_t chunk, hipStream_t st);
+
 // Session close / expire fan-out (close.hip): m closes in fan-out order, grouped by resource.
 struct CloseArgs {
   const uint32_t* cinst;   // [m] instance slots in fan-out order

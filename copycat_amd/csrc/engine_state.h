@@ -30,6 +30,7 @@ int drain_leaks(cc_engine* e);  // the device leak log -> cc_engine::leaks
 // prefix apply, restored when the attempt failed on a fixed capacity
 int ckpt_save(cc_engine* e);
 int ckpt_restore(cc_engine* e);
+int ckpt_reserve(cc_engine* e);  // the checkpoint buffer, allocated before a prefix apply applies its first row
 
 // Occupancy bitmap of a slot space with lowest-free / highest-free search (control-plane allocation: rare, so a
 // word scan from a hint is enough).
@@ -348,6 +349,12 @@ struct cc_engine {
     std::map<uint32_t, std::vector<uint64_t>> leaks;
   } ckpt;
   uint64_t* d_last_index = nullptr;  // index[n-1] of the last batch (device copy)
+  // the stop scan of cc_apply_batch_prefix (prefix_scan.hip; allocated by its first call): per-slot counters and the
+  // list (one allocation), the rank pass's per-chunk counts (grown on demand), the part's event count
+  uint32_t* d_px = nullptr;
+  uint32_t* d_px_bcnt = nullptr;
+  uint64_t px_bcnt_cap = 0;
+  uint64_t* d_px_evn = nullptr;
   // device staging of the host-memory entry points (host_path.hip): grown on demand, kept between calls
   void* hw_buf[24] = {};
   size_t hw_cap[24] = {};

@@ -193,18 +193,31 @@ extern "C" int cc_apply_batch_host_events(cc_engine* e, const cc_batch* h_cols, 
 // a device-to-device copy of every snapshot section into a second allocation of that size, kept until the engine is
 // destroyed), taken whether or not the part then succeeds; a full map table region or a full event stream costs
 // about log2(rows of the part) restores and re-applies on top of it (`attempt` below).
+//
+// cc_apply_batch_prefix (ABI 6) is the same call on device-resident columns: the control flow (prefix_flow) is shared,
+// and what differs -- how a part is applied, how the caller's result rows are kept and put back, and how the next stop
+// is found -- is a PrefixPath.  Its scan runs on the device (prefix_scan.hip): 5 B per row (13 B on lock rows) in one
+// streaming pass plus one thread per resource slot and one 4-byte read back; a non-empty list costs a second streaming
+// pass that ranks the listed resources' rows.  The scan starts from exact block counts, so unlike the host's it is run
+// again on the rest of the batch after every stop: one rescan per stop at streaming speed, which a queue held at
+// coord_cap under churn pays once per add (the host path pays one header read there).
 namespace {
 
-bool adds_entry(uint8_t type, uint8_t op, uint64_t aux) {
-  switch (type) {
-    case CC_RES_LOCK: return op == CC_OP_LOCK_LOCK && aux != 0;  // tryLock() (timeout 0) never queues
-    case CC_RES_ELECTION: return op == CC_OP_ELECT_LISTEN;
-    case CC_RES_GROUP: return op == CC_OP_GROUP_JOIN;
-    case CC_RES_VALUE: return op == CC_OP_VALUE_LISTEN;
-    case CC_RES_QUEUE: return op == CC_OP_QUEUE_ADD || op == CC_OP_QUEUE_OFFER;
-    default: return false;
-  }
-}
+struct PrefixPath {
+  uint64_t ev_n = 0;  // events of the rows applied so far
+  virtual ~PrefixPath() = default;
+  // rows [lo, hi) applied: their results written, their events appended with rows as batch positions (ev_n moves by
+  // the part's events, whether or not they fit)
+  virtual int apply(uint64_t lo, uint64_t hi) = 0;
+  // the caller's result rows [lo, hi) kept aside; rows [from, hi) of the kept ones put back
+  virtual int save(uint64_t lo, uint64_t hi) = 0;
+  virtual int putback(uint64_t from, uint64_t hi) = 0;
+  // rows [0, pos) are applied: the first row from pos on whose resource's bound would pass coord_cap (n: none)
+  virtual int next_stop(uint64_t pos, uint64_t* stop) = 0;
+  virtual int row_res(uint64_t row, uint32_t* r) = 0;  // the resource slot a row addresses (kNoRes: none)
+  virtual void counted(uint32_t, uint32_t) {}          // a block's exact count, read with the rows before applied
+  virtual int finish() = 0;                            // the event count, to where the caller reads it
+};
 
 // apply host rows [lo, hi) appending to the host event stream `hev` (rows shifted to batch positions); *ev_n = events
 // so far
@@ -227,27 +240,23 @@ int apply_part(cc_engine* e, const cc_batch* h, uint64_t lo, uint64_t hi, const 
   return rc;
 }
 
-}  // namespace
-
-extern "C" int cc_apply_batch_host_prefix(cc_engine* e, const cc_batch* h, uint64_t n, const cc_results* hout,
-                                          const cc_events* hev, uint64_t* h_applied) {
-  if (!e || !h || !hout || !h_applied || (n && (!h->inst || !h->op))) return set_err(CC_ERR_INVALID, "null argument");
-  if (hev && (!hev->count || (hev->capacity && (!hev->pos || !hev->target || !hev->code || !hev->src || !hev->tag ||
-                                                !hev->payload))))
-    return set_err(CC_ERR_INVALID, "host event stream: null column or count");
+// The control flow of both prefix applies.  `ck`: the parts run under a device checkpoint (an engine with maps, or a
+// call with an event stream).
+int prefix_flow(cc_engine* e, uint64_t n, bool ck, PrefixPath& p, uint64_t* h_applied) {
   *h_applied = 0;
-  uint64_t ev_n = 0;
   auto finish = [&](int rc) {
-    if (hev) *hev->count = ev_n;
-    return rc;
+    const int rf = p.finish();
+    return rc ? rc : rf;
   };
-  HIPCHECK(hipSetDevice(e->device));
+  if (ck && n) {  // (a call that cannot have its checkpoint fails here, before any row is applied)
+    const int rc = ckpt_reserve(e);
+    if (rc) return finish(rc);
+  }
   // Rows [lo, hi) as one part.  On an engine with maps or with an event stream, a part may also fail on a full map
   // table region or a full event stream (kErrCapacity / kErrEvents, and nothing else): the state before the part is a
   // device checkpoint (ckpt_save), and the longest prefix of the part that applies is found by bisection (restore, apply
   // [lo, mid)); the state is then the one after that prefix, its results and events written, the rows after it keep
   // what the caller had there.  *done = the first row not applied (hi on success).
-  const bool ck = e->map_bits != 0 || hev != nullptr;
   auto cap_only = [&](int rc) {
     const uint32_t b = e->last_err_bits;
     return rc == CC_ERR_CAPACITY && b && !(b & ~(kErrCapacity | kErrEvents));
@@ -255,16 +264,15 @@ extern "C" int cc_apply_batch_host_prefix(cc_engine* e, const cc_batch* h, uint6
   auto attempt = [&](uint64_t lo, uint64_t hi, uint64_t* done) -> int {
     *done = lo;
     if (!ck) {
-      const int rc = apply_part(e, h, lo, hi, hout, hev, &ev_n);
+      const int rc = p.apply(lo, hi);
       if (!rc) *done = hi;
       return rc;
     }
-    std::vector<uint8_t> s0(hout->status + lo, hout->status + hi);  // (the caller's rows, for the rows not applied)
-    std::vector<uint64_t> v0(hout->value + lo, hout->value + hi);
-    const uint64_t ev0 = ev_n;
-    int rc = ckpt_save(e);
+    int rc = p.save(lo, hi);  // (the caller's rows, for the rows not applied)
     if (rc) return rc;
-    rc = apply_part(e, h, lo, hi, hout, hev, &ev_n);
+    const uint64_t ev0 = p.ev_n;
+    if ((rc = ckpt_save(e))) return rc;
+    rc = p.apply(lo, hi);
     if (!rc) {
       *done = hi;
       return CC_OK;
@@ -275,8 +283,8 @@ extern "C" int cc_apply_batch_host_prefix(cc_engine* e, const cc_batch* h, uint6
     while (bad - good > 1) {
       const uint64_t mid = good + (bad - good) / 2;
       if ((rc = ckpt_restore(e))) return rc;
-      ev_n = ev0;
-      rc = apply_part(e, h, lo, mid, hout, hev, &ev_n);
+      p.ev_n = ev0;
+      rc = p.apply(lo, mid);
       if (!rc) {
         good = mid;
         at_good = true;
@@ -289,11 +297,10 @@ extern "C" int cc_apply_batch_host_prefix(cc_engine* e, const cc_batch* h, uint6
     }
     if (!at_good) {
       if ((rc = ckpt_restore(e))) return rc;
-      ev_n = ev0;
-      if (good > lo && (rc = apply_part(e, h, lo, good, hout, hev, &ev_n))) return rc;
+      p.ev_n = ev0;
+      if (good > lo && (rc = p.apply(lo, good))) return rc;
     }
-    std::copy(s0.begin() + (good - lo), s0.end(), hout->status + good);
-    std::copy(v0.begin() + (good - lo), v0.end(), hout->value + good);
+    if ((rc = p.putback(good, hi))) return rc;
     *done = good;
     return CC_ERR_CAPACITY;
   };
@@ -308,53 +315,20 @@ extern "C" int cc_apply_batch_host_prefix(cc_engine* e, const cc_batch* h, uint6
     if (!rc) *h_applied = n;
     return finish(rc);
   }
-  const uint32_t max_inst = e->cfg.max_instances;
-  auto res_of = [&](uint64_t i) -> uint32_t {
-    const uint32_t in = h->inst[i];
-    return in < max_inst ? e->inst_res[in] : kNoRes;
-  };
   const uint32_t cap = e->coord_cap;
   const size_t blk = coord_block(cap);
-  auto adds = [&](uint64_t i, uint32_t r) {
-    return r != kNoRes && r < e->res_type.size() && adds_entry(e->res_type[r], h->op[i], h->aux ? h->aux[i] : 0);
-  };
   auto entries = [&](uint32_t r, uint32_t* out) -> int {  // one block's current entry count (CoordHdr.n)
     CoordHdr hd{};
     HIPCHECK(hipMemcpy(&hd, e->d_coord + (uint64_t)r * blk, sizeof hd, hipMemcpyDeviceToHost));
     *out = hd.n;
     return CC_OK;
   };
-  // the upper bound of every addressed resource's entry count, from one strided copy of the block headers over the
-  // slot range the adding rows address
-  std::unordered_map<uint32_t, uint64_t> bound;
-  {
-    uint32_t rlo = ~0u, rhi = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-      const uint32_t r = res_of(i);
-      if (adds(i, r)) rlo = std::min(rlo, r), rhi = std::max(rhi, r);
-    }
-    if (rlo <= rhi) {
-      std::vector<CoordHdr> hdr(rhi - rlo + 1);
-      HIPCHECK(hipMemcpy2D(hdr.data(), sizeof(CoordHdr), e->d_coord + (uint64_t)rlo * blk, blk, sizeof(CoordHdr),
-                           hdr.size(), hipMemcpyDeviceToHost));
-      for (uint64_t i = 0; i < n; ++i) {
-        const uint32_t r = res_of(i);
-        if (adds(i, r) && !bound.count(r)) bound[r] = hdr[r - rlo].n;
-      }
-    }
-  }
-  uint64_t pos = 0, i = 0;  // rows [0, pos) applied; rows [pos, i) scanned (their adds are in the bounds)
+  uint64_t pos = 0;  // rows [0, pos) applied
   while (pos < n) {
     uint64_t stop = n;  // the first row whose bound would pass coord_cap
-    for (; i < n; ++i) {
-      const uint32_t r = res_of(i);
-      if (!adds(i, r)) continue;
-      uint64_t& b = bound[r];
-      if (b + 1 > cap) {
-        stop = i;
-        break;
-      }
-      ++b;
+    {
+      const int rc = p.next_stop(pos, &stop);
+      if (rc) return finish(rc);
     }
     if (stop > pos) {
       uint64_t done = pos;
@@ -366,14 +340,16 @@ extern "C" int cc_apply_batch_host_prefix(cc_engine* e, const cc_batch* h, uint6
       if (pos == n) break;
     }
     // row pos (= stop) may overflow: its resource's count now (rows before it applied)
-    const uint32_t r = res_of(pos);
-    uint32_t cur = 0;
+    uint32_t r = kNoRes, cur = 0;
     {
-      int rc = entries(r, &cur);
+      int rc = p.row_res(pos, &r);
+      if (!rc && r == kNoRes)
+        rc = set_err(CC_ERR_STATE, "internal check: the stop row of a prefix apply addresses no resource");
+      if (!rc) rc = entries(r, &cur);
       if (rc) return finish(rc);
     }
     if ((uint64_t)cur + 1 <= cap) {  // it fits: the pass goes on from this row with the exact count
-      bound[r] = cur;
+      p.counted(r, cur);
       continue;
     }
     // row pos alone: its resource's block, the clock, the applied index and the group timers are saved first
@@ -385,36 +361,346 @@ extern "C" int cc_apply_batch_host_prefix(cc_engine* e, const cc_batch* h, uint6
     const bool pending = e->applied_pending;
     const uint64_t applied0 = e->applied;
     const auto gtimers = e->gtimers;
-    const uint64_t ev0 = ev_n;
-    const uint8_t st0 = hout->status[pos];
-    const uint64_t va0 = hout->value[pos];
+    const uint64_t ev0 = p.ev_n;
+    if (!ck) {  // (under a checkpoint the attempt keeps the row itself)
+      const int rc = p.save(pos, pos + 1);
+      if (rc) return finish(rc);
+    }
     uint64_t done1 = pos;
     const int rc = attempt(pos, pos + 1, &done1);
     if (rc == CC_ERR_CAPACITY && e->last_err_bits != kErrCoordFull) return full(pos);
     // (only a full coordination collection, and nothing else, is rolled back: any other failure is returned as is)
     if (rc == CC_ERR_CAPACITY && e->last_err_bits == kErrCoordFull) {
-      hout->status[pos] = st0;  // (the row is not applied: its result row keeps what the caller had there)
-      hout->value[pos] = va0;
+      // (the row is not applied: its result row keeps what the caller had there)
+      const int rp = p.putback(pos, pos + 1);
+      if (rp) return finish(rp);
       HIPCHECK(hipMemcpy(e->d_coord + (uint64_t)r * blk, saved.data(), blk, hipMemcpyHostToDevice));
       HIPCHECK(hipMemcpy(e->d_clock, &clock, sizeof clock, hipMemcpyHostToDevice));
       HIPCHECK(hipMemcpy(e->d_last_index, &last, sizeof last, hipMemcpyHostToDevice));
       e->applied_pending = pending;
       e->applied = applied0;
       e->gtimers = gtimers;
-      ev_n = ev0;
+      p.ev_n = ev0;
       return finish(set_err(CC_ERR_CAPACITY, "a coordination collection is full (coord_cap): *applied rows were applied"));
     }
     if (rc) return finish(rc);
     pos += 1;
-    i = pos;
     *h_applied = pos;
     {
-      int rc2 = entries(r, &cur);
+      const int rc2 = entries(r, &cur);
       if (rc2) return finish(rc2);
     }
-    bound[r] = cur;
+    p.counted(r, cur);
   }
   return finish(CC_OK);
+}
+
+// ---- host columns: staged per part by apply_host, results and events in the caller's host memory ---------------------
+struct HostPrefix : PrefixPath {
+  cc_engine* e;
+  const cc_batch* h;
+  uint64_t n;
+  const cc_results* hout;
+  const cc_events* hev;
+  std::vector<uint8_t> s0;  // the kept result rows [s_lo, s_lo + size)
+  std::vector<uint64_t> v0;
+  uint64_t s_lo = 0;
+  std::unordered_map<uint32_t, uint64_t> bound;  // per resource: an upper bound of its block's entry count
+  bool bounded = false;
+  uint64_t i = 0;  // rows before i are scanned (their adds are in the bounds)
+  HostPrefix(cc_engine* e_, const cc_batch* h_, uint64_t n_, const cc_results* o_, const cc_events* v_)
+      : e(e_), h(h_), n(n_), hout(o_), hev(v_) {}
+
+  int apply(uint64_t lo, uint64_t hi) override { return apply_part(e, h, lo, hi, hout, hev, &ev_n); }
+  int save(uint64_t lo, uint64_t hi) override {
+    s0.assign(hout->status + lo, hout->status + hi);
+    v0.assign(hout->value + lo, hout->value + hi);
+    s_lo = lo;
+    return CC_OK;
+  }
+  int putback(uint64_t from, uint64_t hi) override {
+    std::copy(s0.begin() + (from - s_lo), s0.begin() + (hi - s_lo), hout->status + from);
+    std::copy(v0.begin() + (from - s_lo), v0.begin() + (hi - s_lo), hout->value + from);
+    return CC_OK;
+  }
+  uint32_t res_of(uint64_t row) const {
+    const uint32_t in = h->inst[row];
+    return in < e->cfg.max_instances ? e->inst_res[in] : kNoRes;
+  }
+  bool adds(uint64_t row, uint32_t r) const {
+    return r != kNoRes && r < e->res_type.size() && adds_entry(e->res_type[r], h->op[row], h->aux ? h->aux[row] : 0);
+  }
+  // the upper bound of every addressed resource's entry count, from one strided copy of the block headers over the
+  // slot range the adding rows address
+  int bounds() {
+    const size_t blk = coord_block(e->coord_cap);
+    uint32_t rlo = ~0u, rhi = 0;
+    for (uint64_t k = 0; k < n; ++k) {
+      const uint32_t r = res_of(k);
+      if (adds(k, r)) rlo = std::min(rlo, r), rhi = std::max(rhi, r);
+    }
+    if (rlo <= rhi) {
+      std::vector<CoordHdr> hdr(rhi - rlo + 1);
+      HIPCHECK(hipMemcpy2D(hdr.data(), sizeof(CoordHdr), e->d_coord + (uint64_t)rlo * blk, blk, sizeof(CoordHdr),
+                           hdr.size(), hipMemcpyDeviceToHost));
+      for (uint64_t k = 0; k < n; ++k) {
+        const uint32_t r = res_of(k);
+        if (adds(k, r) && !bound.count(r)) bound[r] = hdr[r - rlo].n;
+      }
+    }
+    bounded = true;
+    return CC_OK;
+  }
+  int next_stop(uint64_t pos, uint64_t* stop) override {
+    if (!bounded) {
+      const int rc = bounds();
+      if (rc) return rc;
+    }
+    if (i < pos) i = pos;  // (a row applied alone is not scanned again)
+    for (; i < n; ++i) {
+      const uint32_t r = res_of(i);
+      if (!adds(i, r)) continue;
+      uint64_t& b = bound[r];
+      if (b + 1 > e->coord_cap) break;
+      ++b;
+    }
+    *stop = i;
+    return CC_OK;
+  }
+  int row_res(uint64_t row, uint32_t* r) override {
+    *r = res_of(row);
+    return CC_OK;
+  }
+  void counted(uint32_t r, uint32_t cur) override { bound[r] = cur; }
+  int finish() override {
+    if (hev) *hev->count = ev_n;
+    return CC_OK;
+  }
+};
+
+// ---- device-resident columns (cc_apply_batch_prefix): results and events stay in HBM ---------------------------------
+enum PxSlot : int { kHwSaveStatus = kHwNum, kHwSaveValue, kPxSlots };
+static_assert(kPxSlots <= 24, "cc_engine::hw_buf");
+
+struct DevicePrefix : PrefixPath {
+  cc_engine* e;
+  const cc_batch* c;
+  uint64_t n;
+  const cc_results* out;
+  const cc_events* ev;
+  void* stream;    // as the caller passed it (cc_apply_batch resolves null itself)
+  hipStream_t st;  // the stream every part runs on
+  uint64_t s_lo = 0;
+  DevicePrefix(cc_engine* e_, const cc_batch* c_, uint64_t n_, const cc_results* o_, const cc_events* v_, void* stream_,
+               hipStream_t st_)
+      : e(e_), c(c_), n(n_), out(o_), ev(v_), stream(stream_), st(st_) {}
+
+  // A part that starts at a multiple of four rows meets cc_apply_batch's alignment rules in place (inst and value 16
+  // bytes, status 4).  Any other part (the rest of a batch after a stop, a stop row alone) runs on copies of its
+  // columns in the engine's staging buffers, its results on a copy of the caller's rows that is copied back once it
+  // applied.
+  int apply(uint64_t lo, uint64_t hi) override {
+    const uint64_t m = hi - lo;
+    const bool staged = (lo & 3) != 0;
+    auto sh = [lo](const auto* p) { return p ? p + lo : p; };
+    cc_batch part{sh(c->index), sh(c->time), sh(c->inst), sh(c->op), sh(c->flags), sh(c->key), sh(c->a), sh(c->b),
+                  sh(c->aux)};
+    cc_results o{out->status + lo, out->value + lo};
+    int rc;
+    if (staged) {
+      const void* src[9] = {part.index, part.time, part.inst, part.op, part.flags, part.key, part.a, part.b, part.aux};
+      const size_t esz[9] = {8, 8, 4, 1, 1, 8, 8, 8, 8};
+      void* d[9] = {};
+      for (int k = 0; k < 9; ++k) {
+        if (!src[k]) continue;
+        if ((rc = hw(e, kHwCol + k, esz[k] * m, &d[k]))) return rc;
+        HIPCHECK(hipMemcpyAsync(d[k], src[k], esz[k] * m, hipMemcpyDeviceToDevice, st));
+      }
+      part = cc_batch{(const uint64_t*)d[0], (const uint64_t*)d[1], (const uint32_t*)d[2], (const uint8_t*)d[3],
+                      (const uint8_t*)d[4],  (const uint64_t*)d[5], (const uint64_t*)d[6], (const uint64_t*)d[7],
+                      (const uint64_t*)d[8]};
+      void *ds, *dv;
+      if ((rc = hw(e, kHwStatus, m, &ds)) || (rc = hw(e, kHwValue, 8 * m, &dv))) return rc;
+      HIPCHECK(hipMemcpyAsync(ds, out->status + lo, m, hipMemcpyDeviceToDevice, st));
+      HIPCHECK(hipMemcpyAsync(dv, out->value + lo, 8 * m, hipMemcpyDeviceToDevice, st));
+      o = cc_results{(uint8_t*)ds, (uint64_t*)dv};
+    }
+    cc_events v{};
+    if (ev) {  // the event columns from the events so far on; the part's own count in an engine word
+      v = *ev;
+      const uint64_t k = std::min(ev_n, ev->capacity);
+      v.pos += k, v.target += k, v.code += k, v.src += k, v.tag += k, v.payload += k;
+      v.capacity -= k;
+      v.count = e->d_px_evn;
+      HIPCHECK(hipMemsetAsync(v.count, 0, sizeof(uint64_t), st));
+    }
+    e->last_err_bits = 0;
+    rc = cc_apply_batch(e, &part, m, &o, ev ? &v : nullptr, stream);
+    if (rc) {
+      (void)hipStreamSynchronize(st);
+      return rc;
+    }
+    const int rs = cc_sync(e);  // device-side checks (capacity, unsupported ops, time order)
+    int re = CC_OK;
+    if (ev) {
+      uint64_t cnt = 0;
+      HIPCHECK(hipMemcpyAsync(&cnt, v.count, sizeof cnt, hipMemcpyDeviceToHost, st));
+      HIPCHECK(hipStreamSynchronize(st));
+      if (lo && launch_ev_shift(v.pos, std::min(cnt, v.capacity), (uint32_t)lo, st))
+        return set_err(CC_ERR_HIP, "event row shift launch", hipGetLastError());
+      ev_n += cnt;
+      if (cnt > v.capacity) {
+        e->last_err_bits |= kErrEvents;  // (a full event stream, like a full max_events arena)
+        if (!rs) re = set_err(CC_ERR_CAPACITY, "more events than the event stream holds");
+      }
+    }
+    if (staged && !rs && !re) {
+      HIPCHECK(hipMemcpyAsync(out->status + lo, o.status, m, hipMemcpyDeviceToDevice, st));
+      HIPCHECK(hipMemcpyAsync(out->value + lo, o.value, 8 * m, hipMemcpyDeviceToDevice, st));
+    }
+    HIPCHECK(hipStreamSynchronize(st));
+    return rs ? rs : re;
+  }
+  int save(uint64_t lo, uint64_t hi) override {
+    void *ds, *dv;
+    int rc;
+    if ((rc = hw(e, kHwSaveStatus, hi - lo, &ds)) || (rc = hw(e, kHwSaveValue, 8 * (hi - lo), &dv))) return rc;
+    HIPCHECK(hipMemcpyAsync(ds, out->status + lo, hi - lo, hipMemcpyDeviceToDevice, st));
+    HIPCHECK(hipMemcpyAsync(dv, out->value + lo, 8 * (hi - lo), hipMemcpyDeviceToDevice, st));
+    s_lo = lo;
+    return CC_OK;
+  }
+  int putback(uint64_t from, uint64_t hi) override {
+    if (hi > from) {
+      HIPCHECK(hipMemcpyAsync(out->status + from, (const uint8_t*)e->hw_buf[kHwSaveStatus] + (from - s_lo), hi - from,
+                              hipMemcpyDeviceToDevice, st));
+      HIPCHECK(hipMemcpyAsync(out->value + from, (const uint64_t*)e->hw_buf[kHwSaveValue] + (from - s_lo),
+                              8 * (hi - from), hipMemcpyDeviceToDevice, st));
+    }
+    HIPCHECK(hipStreamSynchronize(st));
+    return CC_OK;
+  }
+  // the scan's buffers: control words (list length, earliest target chunk, stop row), then cnt / list_res /
+  // list_room [slots] and tblk / tbase [kPxGroup]
+  int scan_args(uint64_t lo, PxArgs* a) {
+    const uint32_t slots = (uint32_t)e->sb << kSbShift;
+    if (!e->d_px) HIPCHECK(hipMalloc(&e->d_px, sizeof(uint32_t) * (4 + 3ull * slots + 2 * kPxGroup)));
+    a->inst = c->inst, a->op = c->op, a->aux = c->aux;
+    a->lo = lo, a->hi = n;
+    a->inst_res = e->d_inst_res, a->res_type = e->d_res_type;
+    a->max_inst = e->cfg.max_instances, a->slots = slots;
+    a->coord = e->d_coord, a->coord_cap = e->coord_cap;
+    a->list_n = e->d_px;
+    a->min_tb = e->d_px + 1;
+    a->stop = (unsigned long long*)(e->d_px + 2);
+    a->cnt = e->d_px + 4;
+    a->list_res = a->cnt + slots;
+    a->list_room = a->list_res + slots;
+    a->tblk = a->list_room + slots;
+    a->tbase = a->tblk + kPxGroup;
+    a->bcnt = e->d_px_bcnt;
+    return CC_OK;
+  }
+  int next_stop(uint64_t pos, uint64_t* stop) override {
+    PxArgs a{};
+    int rc = scan_args(pos, &a);
+    if (rc) return rc;
+    if (launch_px_count(a, st)) return set_err(CC_ERR_HIP, "prefix scan launch", hipGetLastError());
+    uint32_t listed = 0;
+    HIPCHECK(hipMemcpyAsync(&listed, a.list_n, sizeof listed, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    *stop = n;
+    if (!listed) return CC_OK;  // (the normal case: no resource's bound passes coord_cap in [pos, n))
+    // the rank pass: [pos, n) in at most kPxMaxBlocks chunks of whole tiles, kPxGroup listed resources at a time
+    const uint64_t len = n - pos, tiles = (len + kPxBlock - 1) / kPxBlock;
+    const uint64_t chunk = (tiles + kPxMaxBlocks - 1) / kPxMaxBlocks * kPxBlock;
+    const uint32_t nblk = (uint32_t)((len + chunk - 1) / chunk);
+    const uint64_t need = (uint64_t)nblk * std::min(listed, kPxGroup);
+    if (need > e->px_bcnt_cap) {
+      if (e->d_px_bcnt) HIPCHECK(hipFree(e->d_px_bcnt));
+      e->d_px_bcnt = nullptr;
+      e->px_bcnt_cap = 0;
+      HIPCHECK(hipMalloc(&e->d_px_bcnt, sizeof(uint32_t) * need));
+      e->px_bcnt_cap = need;
+    }
+    a.bcnt = e->d_px_bcnt;
+    for (uint32_t g0 = 0; g0 < listed; g0 += kPxGroup)
+      if (launch_px_rank(a, g0, std::min(listed - g0, kPxGroup), nblk, chunk, st))
+        return set_err(CC_ERR_HIP, "prefix rank launch", hipGetLastError());
+    unsigned long long row = ~0ull;
+    HIPCHECK(hipMemcpyAsync(&row, a.stop, sizeof row, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (row < pos || row >= n)
+      return set_err(CC_ERR_STATE, "internal check: the prefix scan listed a resource but ranked no stop row");
+    *stop = row;
+    return CC_OK;
+  }
+  int row_res(uint64_t row, uint32_t* r) override {
+    uint32_t in = 0;
+    HIPCHECK(hipMemcpyAsync(&in, c->inst + row, sizeof in, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    *r = in < e->cfg.max_instances ? e->inst_res[in] : kNoRes;
+    return CC_OK;
+  }
+  int finish() override {
+    if (!ev) return CC_OK;
+    HIPCHECK(hipMemcpyAsync(ev->count, &ev_n, sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipStreamSynchronize(st));  // (ev_n is a member of a local)
+    return CC_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" int cc_apply_batch_host_prefix(cc_engine* e, const cc_batch* h, uint64_t n, const cc_results* hout,
+                                          const cc_events* hev, uint64_t* h_applied) {
+  if (!e || !h || !hout || !h_applied || (n && (!h->inst || !h->op))) return set_err(CC_ERR_INVALID, "null argument");
+  if (hev && (!hev->count || (hev->capacity && (!hev->pos || !hev->target || !hev->code || !hev->src || !hev->tag ||
+                                                !hev->payload))))
+    return set_err(CC_ERR_INVALID, "host event stream: null column or count");
+  *h_applied = 0;
+  HIPCHECK(hipSetDevice(e->device));
+  HostPrefix p(e, h, n, hout, hev);
+  return prefix_flow(e, n, e->map_bits != 0 || hev != nullptr, p, h_applied);
+}
+
+extern "C" int cc_apply_batch_prefix(cc_engine* e, const cc_batch* c, uint64_t n, const cc_results* out,
+                                     const cc_events* ev, void* stream, uint64_t* h_applied) {
+  if (!e || !c || !out || !h_applied) return set_err(CC_ERR_INVALID, "null argument");
+  if (ev && (!ev->pos || !ev->target || !ev->code || !ev->src || !ev->tag || !ev->payload || !ev->count))
+    return set_err(CC_ERR_INVALID, "event stream columns and count are required");
+  *h_applied = 0;
+  HIPCHECK(hipSetDevice(e->device));
+  hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
+  if (n == 0) {
+    if (ev) {
+      HIPCHECK(hipMemsetAsync(ev->count, 0, sizeof(uint64_t), st));
+      HIPCHECK(hipStreamSynchronize(st));
+    }
+    return CC_OK;
+  }
+  // cc_apply_batch's own argument rules, checked before the scan reads a column or a checkpoint is taken
+  if (n > e->cfg.max_batch) return set_err(CC_ERR_CAPACITY, "batch larger than max_batch");
+  if (!c->inst || !c->op || !c->flags || !c->a || !c->b || !out->status || !out->value)
+    return set_err(CC_ERR_INVALID, "inst/op/flags/a/b columns and status/value outputs are required");
+  if ((((uintptr_t)out->status) & 3) || (((uintptr_t)out->value) & 15) || (((uintptr_t)c->inst) & 15))
+    return set_err(CC_ERR_INVALID, "inst and value must be 16-byte aligned, status 4-byte aligned");
+  if (st != e->last_stream) HIPCHECK(hipStreamSynchronize(e->last_stream));
+  e->last_stream = st;
+  if (!e->coord_on && !e->map_bits && !ev) {  // nothing here can fill: the plain call and the final sync
+    int rc = cc_apply_batch(e, c, n, out, nullptr, stream);
+    if (rc) {
+      (void)hipStreamSynchronize(st);
+      return rc;
+    }
+    if (!(rc = cc_sync(e))) *h_applied = n;
+    return rc;
+  }
+  int rc = quiesce(e);  // (queued registry writes: the scan reads the device registry)
+  if (rc) return rc;
+  if (ev && !e->d_px_evn) HIPCHECK(hipMalloc(&e->d_px_evn, sizeof(uint64_t)));
+  DevicePrefix p(e, c, n, out, ev, stream, st);
+  return prefix_flow(e, n, e->map_bits != 0 || ev != nullptr, p, h_applied);
 }
 
 extern "C" int cc_sessions_close_host(cc_engine* e, const uint64_t* h_clients, uint64_t count, const cc_events* h_events,

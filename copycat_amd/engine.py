@@ -106,6 +106,7 @@ def lib():
             "cc_wire_decode": (i32, [P, P, P, P, u64, P, u64, P, P]),
             "cc_split_batch": (i32, [P, u64, P, u32, u32, u32, P, P, P, P]),
             "cc_apply_batch_host_prefix": (i32, [P, P, u64, P, P, P]),
+            "cc_apply_batch_prefix": (i32, [P, P, u64, P, P, P, P]),
             "cc_merge_results": (i32, [P, u64, P, u32, u32, u32, P, P]),
         }
         for name, (res, args) in sig.items():
@@ -369,6 +370,22 @@ class Engine:
             _check(rc)
         m = int(min(count[0], cap))
         return applied.value, status, value, {k: v[:m] for k, v in cols.items()}
+
+    def apply_prefix(self, db: DeviceBatch, status, value, events: "DeviceEvents" = None, stream=None):
+        """cc_apply_batch_prefix: apply() / apply_events() with the stop-before-row contract of apply_host_prefix on
+        device-resident columns.  Returns the rows applied: db.n on success, fewer when the next row meets a full
+        coordination collection, map table region or event stream (the engine state, `status` / `value` rows and
+        `events` are then exactly those after the applied rows; the rows from there on keep what the tensors held).
+        Synchronous.  Any other failure raises."""
+        s = db.struct()
+        r = abi.cc_results(status.data_ptr(), value.data_ptr())
+        ev = events.struct() if events is not None else None
+        applied = C.c_uint64()
+        rc = self.L.cc_apply_batch_prefix(self.h, C.byref(s), db.n, C.byref(r), C.byref(ev) if ev is not None else None,
+                                          _stream_ptr(stream), C.byref(applied))
+        if rc not in (abi.CC_OK, abi.CC_ERR_CAPACITY) or (rc == abi.CC_ERR_CAPACITY and applied.value >= db.n):
+            _check(rc)
+        return applied.value
 
     def sync(self):
         _check(self.L.cc_sync(self.h))

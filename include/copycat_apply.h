@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define CC_ABI_VERSION 5
+#define CC_ABI_VERSION 6
 
 /* ---- return codes ------------------------------------------------------------------------------ */
 #define CC_OK               0
@@ -538,6 +538,23 @@ int  cc_wire_decode(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* 
  * events are those after the rows before it.  A host with a full event stream drains it and resumes at that row. */
 int  cc_apply_batch_host_prefix(cc_engine* e, const cc_batch* h_cols, uint64_t n, const cc_results* h_out,
                                 const cc_events* h_events, uint64_t* h_applied);
+
+/* ---- the same contract on device-resident columns (ABI 6; copycat_amd/csrc/host_path.hip, prefix_scan.hip) ----
+ * cc_apply_batch with the stop-before-row contract of cc_apply_batch_host_prefix.  d_cols, d_out and d_events (may be
+ * NULL) hold device pointers, d_events->count included, under cc_apply_batch's argument and alignment rules;
+ * h_applied is a host pointer.  The call is synchronous: on return the stream is drained and the results are final.
+ *   success: CC_OK, *h_applied = n; results, events, state and applied index are those of one cc_apply_batch.
+ *   a full coordination collection, map table region or event stream (d_events->capacity or max_events):
+ *     CC_ERR_CAPACITY with *h_applied = r < n; the state is exactly the one after rows [0, r), d_out rows [0, r) are
+ *     written, rows [r, n) keep byte for byte what the caller had there, and *d_events->count = the events of rows
+ *     [0, r), all present, pos relative to the batch, in publish order.
+ *   any other failure is returned as it is.  n == 0: CC_OK, *h_applied = 0 (and *d_events->count = 0).  A NULL
+ *   h_applied fails with CC_ERR_INVALID before anything runs; a checkpoint buffer that cannot be allocated fails the
+ *   call before any row is applied.
+ * The rows that may overflow a coordination collection are found on the device (no column is copied to the host);
+ * on an engine with no coordination resources, no maps and no event stream the call is cc_apply_batch + cc_sync. */
+int  cc_apply_batch_prefix(cc_engine* e, const cc_batch* d_cols, uint64_t n, const cc_results* d_out,
+                           const cc_events* d_events, void* stream, uint64_t* h_applied);
 
 /* ---- one global log, many engines (ABI 5; copycat_amd/csrc/split.cpp) -----------------------------
  * The reference multiplexes every resource in one Raft log (ResourceManager.java:37-39,56-72); with one engine per
