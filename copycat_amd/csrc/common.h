@@ -188,6 +188,10 @@ __host__ __device__ inline uint32_t mmap_as_map_op(uint32_t op, uint32_t tag_a) 
   }
   return 0;
 }
+// a keyed resource's op as the MapState op it behaves like (a map's ops are themselves)
+__host__ __device__ inline uint32_t keyed_as_map_op(uint32_t type, uint32_t op, uint32_t tag_a) {
+  return type == CC_RES_SET ? set_as_map_op(op) : type == CC_RES_MULTIMAP ? mmap_as_map_op(op, tag_a) : op;
+}
 // ops this build applies on the GPU (others raise CC_ERR_UNSUPPORTED for the batch)
 __host__ __device__ inline bool op_on_gpu(uint32_t type, uint32_t op) {
   if (type == CC_RES_VALUE) return op == CC_OP_DELETE || (op >= 50 && op <= 53);

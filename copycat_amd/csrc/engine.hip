@@ -1075,9 +1075,10 @@ extern "C" int cc_apply_batch(cc_engine* e, const cc_batch* c, uint64_t n, const
   e->clr_heavy.clear();
   if (e->map_bits || e->coord_on) {
     uint32_t nb = 0, ttl_seen = 0;
-    // Outside TTL mode map size / isEmpty, containsValue and clear rows are answered in the stream (listed, their maps
-    // flagged); in TTL mode size / isEmpty rows are (the event replay answers them), the others are barriers.  A batch
-    // that turns TTL mode on (or lists more than a list holds) is scanned again with TTL mode's lists (or larger ones).
+    // Outside TTL mode the size / isEmpty, clear / removeValue and Delete rows of maps, sets and multimaps and a map's
+    // containsValue rows are answered in the stream (listed, their slots flagged); in TTL mode size / isEmpty rows are
+    // (the event replay answers them), the others are barriers.  A batch that turns TTL mode on (or lists more than a
+    // list holds) is scanned again with TTL mode's lists (or larger ones).
     bool inline_size = e->map_bits && !e->ttl_live;
     bool inline_ttl = e->map_bits && e->ttl_live;
     for (int pass = 0;; ++pass) {
@@ -1754,6 +1755,7 @@ extern "C" int cc_apply_batch(cc_engine* e, const cc_batch* c, uint64_t n, const
           sz.op = c->op;
           sz.index = c->index;
           sz.inst_res = e->d_inst_res;
+          sz.res_type = e->d_res_type;
           sz.ev_key = e->d_sm_key;
           sz.ev_val = e->d_sm_val;
           sz.ev_pay = e->d_sm_pay;
@@ -1817,6 +1819,7 @@ extern "C" int cc_apply_batch(cc_engine* e, const cc_batch* c, uint64_t n, const
           sz.op = c->op;
           sz.index = c->index;
           sz.inst_res = e->d_inst_res;
+          sz.res_type = e->d_res_type;
           sz.ev_key = e->d_sm_key;
           sz.ev_val = e->d_sm_val;
           sz.ev_pay = e->d_sm_pay;

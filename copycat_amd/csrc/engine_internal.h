@@ -244,6 +244,7 @@ struct SizeArgs {
   const uint8_t* op;
   const uint64_t* index;
   const uint32_t* inst_res;
+  const uint8_t* res_type;      // (a set's / multimap's isEmpty is told from its size by the op its type maps it to)
   uint64_t* ev_key;
   uint32_t* ev_val;
   EvPay* ev_pay;
@@ -272,8 +273,10 @@ int launch_map_rows(const uint16_t* cpos, uint64_t lo, uint64_t hi, uint32_t* ma
 // Whole-map ops (containsValue / isEmpty / size / clear / Delete): barrier rows of a batch (map_wide.hip).
 constexpr uint32_t kBarCap = 1u << 16;  // barrier rows per batch
 // Also flags (ttl_seen = 1) a map put/putIfAbsent/replace/replaceIfPresent row with ttl > 0.
-// Outside TTL mode map size / isEmpty rows are not barriers: they are listed in szq (rows) and their maps flagged
-// (kMfSize in mflag), then answered in the stream (map_small.hip launch_size_answer).
+// The size / isEmpty rows of maps, sets and multimaps are not barriers: they are listed in szq (rows) and their slots
+// flagged (kMfSize in mflag), then answered in the stream (map_small.hip launch_size_answer; TTL mode: k_ttl_replay).
+// Outside TTL mode their clear / removeValue / Delete rows are listed in clrq (map_clear.hip) and a map's containsValue
+// rows in cvq (map_cv.hip).
 int launch_map_barriers(const uint32_t* inst, const uint8_t* op, const uint64_t* aux, uint64_t n, const uint32_t* inst_res,
                         const uint8_t* res_type, uint32_t max_inst, uint32_t* bar, uint32_t* bar_n, uint32_t cap,
                         uint32_t* ttl_seen, uint32_t* szq, uint32_t* szq_n, uint32_t szq_cap, uint8_t* mflag,
@@ -293,7 +296,7 @@ struct CvBatchArgs {  // per batch: classify the candidates listed by k_map_barr
   const uint32_t* cvq;
   const uint32_t* cvq_n;
   uint32_t cvq_cap;
-  uint32_t* mfirst;   // per map: the first row that stores a null or deletes the map (~0: none)
+  uint32_t* mfirst;   // per map: the first row that stores a null (~0: none)
   uint8_t* maynull;   // per map: holds a null value at the batch start
   uint32_t R;
   uint32_t* bar;

@@ -1,4 +1,8 @@
-// map_clear.hip — MapState.clear applied in the stream, outside TTL mode.
+// map_clear.hip — MapState.clear applied in the stream, outside TTL mode; and with it every row that empties a keyed
+// collection the same way: MapState.delete (:264-274, the map's DeleteCommand), SetState.clear / delete,
+// MultiMapState.removeValue / clear / delete (a set's elements and a multimap's keys are map keys holding Boolean
+// TRUE, common.h; every value map of a multimap is empty, so removeValue drops every key).  "Map" and "clear" below
+// stand for any of these slots and rows: k_map_barriers lists them all, and nothing here looks at the op again.
 //
 // MapState.clear (collections/src/main/java/io/atomix/collections/state/MapState.java:255-274) removes every entry of
 // the map (its iterator removes them one by one, cancelling their timers; with no timer the result is an empty map
@@ -8,8 +12,8 @@
 //   per batch      k_map_barriers lists the map clear rows (common.h ClrCtx); the list is sorted by (map, row) with
 //                  per-map offsets (k_clr_keys, k_clr_off);
 //   per sub-batch  k_clr_sub flags the maps cleared in the sub-batch (kMfClr) and gives every map its clears before
-//                  the sub-batch and within it (at most 127: the host
-//                  ends a sub-batch earlier for a map cleared more often); a commit's epoch is the clears of its map
+//                  the sub-batch and within it (at most 127, every clear-class row counted: the host
+//                  ends a sub-batch earlier for a slot cleared more often); a commit's epoch is the clears of its map
 //                  in [lo, row) (k_apply_map, at the top of its chunk: MRec meta bits 25-31 in LDS); a commit whose
 //                  epoch differs from the one its entry's state is at (the previous commit of the entry, or the epoch
 //                  the entry reached in an earlier chunk) sees the entry absent before it -- the transformer CLEAR.el

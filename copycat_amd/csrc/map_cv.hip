@@ -7,7 +7,8 @@
 //
 //   per batch   k_map_barriers lists the containsValue rows of maps (candidates) and flags their maps (kMfCv);
 //               k_cv_nullrows finds, per flagged map, the first row that stores a null value (put / putIfAbsent /
-//               replace / replaceIfPresent with a NULL value tag) or deletes the map; k_cv_maynull marks the flagged
+//               replace / replaceIfPresent with a NULL value tag) (a clear or a Delete of the map stores none and is
+//               an epoch of the stream, map_clear.hip: neither counts); k_cv_maynull marks the flagged
 //               maps that hold a null at the batch start; k_cv_classify keeps a candidate in the stream when its map
 //               holds no null before it (else it becomes a barrier row, answered by map_wide.hip in HashMap order);
 //   per sub-batch  the in-stream rows' operands go into a device hash set (k_cv_query, one position per operand,
@@ -33,7 +34,8 @@ __device__ inline bool cv_stores(uint32_t op) {
   return op == CC_OP_MAP_PUT || op == CC_OP_MAP_PUTIFABSENT || op == CC_OP_MAP_REPLACE || op == CC_OP_MAP_REPLACEIFPRESENT;
 }
 
-// per batch: the first row of each flagged map that stores a null (or deletes the map: k_map_barriers lists those).
+// per batch: the first row of each flagged map that stores a null.  (A Delete is no such row: it removes the map's
+// nulls and is applied in the stream as a clear epoch, map_clear.hip; the count of a containsValue after it restarts.)
 // 16 rows per thread and step from one 16-byte load of the op and flags columns each (a row per thread with byte
 // loads was 1.9 ms per 1e9 rows); the rare null-storing rows resolve their map.
 __device__ inline void cv_null_row(uint64_t i, const uint32_t* __restrict__ inst, const uint32_t* __restrict__ inst_res,

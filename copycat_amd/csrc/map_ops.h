@@ -95,8 +95,10 @@ __device__ inline uint32_t map_orphan(uint32_t op, uint32_t meta, uint32_t flags
   if (!op_registered(CC_RES_MAP, op)) return CC_STATUS(CC_ST_UNKNOWN_OP, CC_TAG_NULL);
   // size / isEmpty are answered in the stream after the sub-batch (map_small.hip k_size_answer; k_ttl_replay in TTL mode),
   // containsValue rows that reach a region (the batch answers them in the stream) by map_cv.hip k_cv_answer; a clear
-  // that reaches a region is applied in the stream (map_clear.hip: MapState.clear returns nothing)
-  if (op == CC_OP_MAP_SIZE || op == CC_OP_MAP_ISEMPTY || op == CC_OP_MAP_CONTAINSVALUE || op == CC_OP_MAP_CLEAR)
+  // or a Delete that reaches a region is applied in the stream (map_clear.hip: MapState.clear / delete return nothing).
+  // A set's and a multimap's whole-collection rows arrive here as these ops (k_part_ext rewrites them).
+  if (op == CC_OP_MAP_SIZE || op == CC_OP_MAP_ISEMPTY || op == CC_OP_MAP_CONTAINSVALUE || op == CC_OP_MAP_CLEAR ||
+      op == CC_OP_DELETE)
     return CC_STATUS(CC_ST_OK, CC_TAG_NULL);
   if (!map_key_op(op) || (map_reads_ttl(op) && (meta & kMetaTtl))) {
     err |= kErrUnsupported;

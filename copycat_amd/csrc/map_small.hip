@@ -422,7 +422,8 @@ __global__ void k_small_clear(SmallMap* __restrict__ st, uint32_t m) {
   }
 }
 
-// ---- map size / isEmpty in the stream (MapState.size :233-239, isEmpty :244-250), outside TTL mode ---------------
+// ---- size / isEmpty in the stream (MapState.size :233-239, isEmpty :244-250; SetState's and MultiMapState's alike:
+//      their elements / keys are map keys) ---------------------------------------------------------------------
 // The size at a row is the size at the sub-batch's end (the exact tracking, msize) minus the map's net insertions of
 // the sub-batch, plus those before the row.  The map's insertions / removals are the events k_msize_count emits for
 // flagged maps; the queries join them in the same buffer (key bit 3, after the commit whose index they carry: a
@@ -432,8 +433,9 @@ __global__ void k_small_clear(SmallMap* __restrict__ st, uint32_t m) {
 __global__ void k_size_emit(const uint32_t* __restrict__ szq, uint32_t szq_n, uint64_t lo, uint64_t hi,
                             const uint32_t* __restrict__ inst, const uint8_t* __restrict__ op,
                             const uint64_t* __restrict__ index, const uint32_t* __restrict__ inst_res,
-                            uint64_t* __restrict__ ev_key, uint32_t* __restrict__ ev_val, EvPay* __restrict__ ev_pay,
-                            uint32_t cap, uint32_t* __restrict__ ctl, bool ttl, uint32_t* __restrict__ err) {
+                            const uint8_t* __restrict__ res_type, uint64_t* __restrict__ ev_key,
+                            uint32_t* __restrict__ ev_val, EvPay* __restrict__ ev_pay, uint32_t cap,
+                            uint32_t* __restrict__ ctl, bool ttl, uint32_t* __restrict__ err) {
   const uint64_t idx0 = ttl ? 0 : index[lo];
   for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < szq_n; q += gridDim.x * blockDim.x) {
     const uint32_t row = szq[q];
@@ -443,7 +445,9 @@ __global__ void k_size_emit(const uint32_t* __restrict__ szq, uint32_t szq_n, ui
     if (d >> kEvPosBits) atomicOr(err, kErrSpan);
     const uint32_t at = atomicAdd(ctl, 1u);
     if (at < cap) {
-      ev_key[at] = ((uint64_t)m << kEvMapShift) | ((d & kEvPosMask) << 4) | 8u | (op[row] == CC_OP_MAP_ISEMPTY ? 4u : 0u);
+      // (the op as the row's type maps it: SetState.isEmpty and MultiMapState.isEmpty are MapState.isEmpty here)
+      const bool empty_q = keyed_as_map_op(res_type[m], op[row], CC_TAG_NULL) == CC_OP_MAP_ISEMPTY;
+      ev_key[at] = ((uint64_t)m << kEvMapShift) | ((d & kEvPosMask) << 4) | 8u | (empty_q ? 4u : 0u);
       ev_val[at] = at;
       ev_pay[at] = EvPay{0, row, 0};
     }
@@ -534,7 +538,8 @@ int launch_small_fold(uint8_t* left, uint8_t* msmall, uint32_t R, hipStream_t st
 int launch_size_emit(const SizeArgs& a, hipStream_t st) {
   if (a.szq_n == 0) return 0;
   hipLaunchKernelGGL(k_size_emit, dim3(std::min<uint32_t>(1024, (a.szq_n + 255) / 256)), dim3(256), 0, st, a.szq, a.szq_n,
-                     a.lo, a.hi, a.inst, a.op, a.index, a.inst_res, a.ev_key, a.ev_val, a.ev_pay, a.cap, a.ctl, a.ttl, a.err);
+                     a.lo, a.hi, a.inst, a.op, a.index, a.inst_res, a.res_type, a.ev_key, a.ev_val, a.ev_pay, a.cap, a.ctl, a.ttl,
+                     a.err);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

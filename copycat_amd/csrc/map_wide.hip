@@ -3,9 +3,14 @@
 // :264-274) (collections/src/main/java/io/atomix/collections/state/MapState.java).
 //
 // A map's keys are spread over every table region (apply_map.hip), so these ops cannot run inside the region
-// kernel.  They are *barriers*: cc_apply_batch finds them first (k_map_barriers), applies the rows between two
-// barriers as an ordinary segment (partition + region apply), then applies the barrier row against the table as
-// it stands at that log position:
+// kernel.  cc_apply_batch finds them first (k_map_barriers).  Outside TTL mode most of them are then ordinary rows of
+// the stream, on every keyed type (a set's elements and a multimap's keys are map keys, common.h keyed_as_map_op):
+// size / isEmpty are answered from the size tracking (map_small.hip), clear / removeValue / Delete are epochs
+// (map_clear.hip), a containsValue on a map that holds no null is counted (map_cv.hip).  What remains is a *barrier*:
+// a containsValue on a map that may hold a null (its answer depends on iteration order), MembershipGroup.schedule (a
+// host timer), and in TTL mode every whole-collection row but size / isEmpty (an entry's liveness then depends on
+// the clock at the row).  cc_apply_batch applies the rows between two barriers as an ordinary segment (partition +
+// region apply), then applies the barrier row against the table as it stands at that log position:
 //   k_mw_count   every entry of the map: live size, bound entries, stored nulls, values equal to the operand;
 //   k_mw_order   containsValue only, when the answer depends on java.util.HashMap iteration order (the map
 //                stores a null AND a match: the first of them in iteration order decides NPE vs true, A5);
@@ -59,7 +64,7 @@ __device__ inline void map_barrier_row(uint64_t i, uint32_t o, const uint32_t* _
                                        const uint64_t* __restrict__ aux, const uint32_t* __restrict__ inst_res,
                                        const uint8_t* __restrict__ res_type, uint32_t max_inst,
                                        uint32_t* __restrict__ ttl_seen, bool szq, uint8_t* __restrict__ mflag, bool cvq,
-                                       uint32_t* __restrict__ mfirst, bool clrq, Push push) {
+                                       bool clrq, Push push) {
   bool wide = map_wide_op(o) || set_wide_op(o) || mmap_wide_op(o) || o == CC_OP_GROUP_SCHEDULE;
   const bool ttl = aux && ttl_op(o);
   if (!wide && !ttl) return;
@@ -77,10 +82,13 @@ __device__ inline void map_barrier_row(uint64_t i, uint32_t o, const uint32_t* _
   else if (ty == CC_RES_GROUP) wide = o == CC_OP_GROUP_SCHEDULE;  // MembershipGroupState.schedule: a timer
   else return;
   if ((ty == CC_RES_GROUP || ty == CC_RES_MULTIMAP) && !wide) return;
-  if (szq && ty == CC_RES_MAP && (o == CC_OP_MAP_SIZE || o == CC_OP_MAP_ISEMPTY)) {
-    // MapState.size / isEmpty (:233-250): an ordinary row, answered from the exact size tracking (k_size_answer; in
-    // TTL mode from the event replay, k_ttl_replay); its map's insertions and removals of the batch are followed
-    // (mflag bit 1)
+  // the whole-collection op as the MapState op it behaves like (common.h: a set's elements and a multimap's keys are
+  // map keys; removeValue / clear / Delete of every keyed type empty the collection as MapState.clear does)
+  const uint32_t mo = wide && is_keyed(ty) ? keyed_as_map_op(ty, o, CC_TAG_NULL) : 0u;
+  if (szq && (mo == CC_OP_MAP_SIZE || mo == CC_OP_MAP_ISEMPTY)) {
+    // MapState.size / isEmpty (:233-250), SetState.size / isEmpty, MultiMapState.isEmpty: an ordinary row, answered
+    // from the exact size tracking (k_size_answer; in TTL mode from the event replay, k_ttl_replay); its slot's
+    // insertions and removals of the batch are followed (mflag bit 1)
     push(kLsSz, (uint32_t)i);
     if (!(mflag[r] & kMfSize)) mflag_or(mflag, r, kMfSize);
     return;
@@ -92,12 +100,13 @@ __device__ inline void map_barrier_row(uint64_t i, uint32_t o, const uint32_t* _
     if (!(mflag[r] & kMfCv)) mflag_or(mflag, r, kMfCv);
     return;
   }
-  if (clrq && ty == CC_RES_MAP && o == CC_OP_MAP_CLEAR) {
-    // MapState.clear (:255-274) outside TTL mode: applied in the stream as an epoch (map_clear.hip)
-    push(kLsClr, (uint32_t)i);  // (k_clr_sub flags the map in the sub-batches that clear it)
+  if (clrq && (mo == CC_OP_MAP_CLEAR || mo == CC_OP_DELETE)) {
+    // MapState.clear / delete (:255-274), SetState.clear / delete, MultiMapState.removeValue / clear / delete outside
+    // TTL mode: applied in the stream as an epoch (map_clear.hip).  A Delete removes the map's nulls and stores none,
+    // so like clear it leaves mfirst alone: containsValue rows after it stay candidates for the stream.
+    push(kLsClr, (uint32_t)i);  // (k_clr_sub flags the slot in the sub-batches that clear it)
     return;
   }
-  if (mfirst && ty == CC_RES_MAP && o == CC_OP_DELETE) atomicMin(&mfirst[r], (uint32_t)i);  // (k_cv_classify)
   if (!wide) {
     // not a barrier here: a row that arms a TTL timer on this map / set?
     if (!aux || !(ty == CC_RES_MAP ? ttl_op(o) && o != CC_OP_SET_ADD : o == CC_OP_SET_ADD) || (int64_t)aux[i] <= 0) return;
@@ -128,8 +137,8 @@ __global__ __launch_bounds__(kMwT) void k_map_barriers(const uint32_t* __restric
                                                       uint32_t* __restrict__ szq_n, uint32_t szq_cap,
                                                       uint8_t* __restrict__ mflag, uint32_t* __restrict__ cvq,
                                                       uint32_t* __restrict__ cvq_n, uint32_t cvq_cap,
-                                                      uint32_t* __restrict__ mfirst, uint32_t* __restrict__ clrq,
-                                                      uint32_t* __restrict__ clrq_n, uint32_t clrq_cap) {
+                                                      uint32_t* __restrict__ clrq, uint32_t* __restrict__ clrq_n,
+                                                      uint32_t clrq_cap) {
   static_assert(kMwT == 256, "one candidate-table entry per thread");
   __shared__ uint32_t lrow[kLists][kMwStage];
   __shared__ uint32_t lcnt[kLists], lbase[kLists];
@@ -196,7 +205,7 @@ __global__ __launch_bounds__(kMwT) void k_map_barriers(const uint32_t* __restric
         if (i >= n) continue;
         const uint32_t o = op[i];
         map_barrier_row(i, o, inst, aux, inst_res, res_type, max_inst, ttl_seen, szq != nullptr, mflag, cvq != nullptr,
-                        mfirst, clrq != nullptr, push);
+                        clrq != nullptr, push);
       }
     }
   }
@@ -611,13 +620,14 @@ int launch_map_barriers(const uint32_t* inst, const uint8_t* op, const uint64_t*
   if (szq_n && hipMemsetAsync(szq_n, 0, sizeof(uint32_t), st) != hipSuccess) return -1;
   if (cvq_n && hipMemsetAsync(cvq_n, 0, sizeof(uint32_t), st) != hipSuccess) return -1;
   if (clrq_n && hipMemsetAsync(clrq_n, 0, sizeof(uint32_t), st) != hipSuccess) return -1;
+  // (mfirst: the first row of each map that stores a null, filled by map_cv.hip k_cv_nullrows after this scan)
   if (mfirst && hipMemsetAsync(mfirst, 0xFF, sizeof(uint32_t) * R, st) != hipSuccess) return -1;
   // persistent: 8 workgroups per CU at most (each wave then takes ~30 4-KB steps of a 1e9-row batch)
   const uint64_t steps = (n + kMwWaveBytes - 1) / kMwWaveBytes, wpg = kMwT / kWave;
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(8 * kPersistGrid, (steps + wpg - 1) / wpg));
   hipLaunchKernelGGL(k_map_barriers, dim3(grid), dim3(kMwT), 0, st, inst, op, aux, n, inst_res,
-                     res_type, max_inst, bar, bar_n, cap, ttl_seen, szq, szq_n, szq_cap, mflag, cvq, cvq_n, cvq_cap, mfirst,
-                     clrq, clrq_n, clrq_cap);
+                     res_type, max_inst, bar, bar_n, cap, ttl_seen, szq, szq_n, szq_cap, mflag, cvq, cvq_n, cvq_cap, clrq,
+                     clrq_n, clrq_cap);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -379,8 +379,9 @@ __global__ __launch_bounds__(kPT, 4) void k_part_ext(
         // map slot | row in the tile << 17 (MRec.rr: replaceIfPresent's b is read from the batch by row)
         xs[j] = res[j] | ((uint32_t)(w * (kWave * J) + j * kWave + l + ch * C) << 17);
         if ((int64_t)xa[j] > 0 && ty != CC_RES_MULTIMAP) meta[j] |= kMetaTtl;
-        // a map cleared in this sub-batch: the commit's clear epoch (the map kernels read it from the meta word)
-        if (clr.mflag && ty == CC_RES_MAP)  // (0 for a map not cleared in the sub-batch: one load, no flag test)
+        // a map / set / multimap cleared in this sub-batch: the commit's clear epoch (the map kernels read it from the
+        // meta word)
+        if (clr.mflag)  // (0 for a slot not cleared in the sub-batch: one load, no flag test)
           meta[j] |= clr_epoch(clr, res[j], cbase + (uint64_t)w * (kWave * J) + (uint64_t)j * kWave + l) << kMetaEpochShift;
       } else if (tyb & kTpWalk) {
         value_encode(meta[j] & 0xFF, (meta[j] >> 8) & 0xFF, ab[j].x, ab[j].y, meta[j], ab[j]);
