@@ -333,33 +333,56 @@ __global__ __launch_bounds__(kP4T) void k_part_v4(const uint32_t* __restrict__ i
 // waves 4-15 load, decode, rank and place the next chunk (3072 records) into the other LDS buffer and store the
 // previous chunk's results.  The super-bucket's list is its run in every 8192-commit tile, in tile (= log) order.
 //
-// Per chunk the loaders (`prepare`): read the results of the chunk before the walked one out of LDS, rank their
-// records into per-wave slot counters, and arrive on the LDS counter `lbar`.  ONE loader wave (a different one each
-// chunk) waits for the twelve arrivals, turns the counters in place into placement bases (slot start + the counts
-// of the waves before, k_part_v4's wave-0 scan) and the walkers' slot starts, and posts on `lbar` again.  The other
-// eleven meanwhile do everything that does not need the bases: they pack and store the results, decode their
-// records into registers, and look up and issue the loads of the chunk after; then they wait for that post.  (The
-// scanning wave does the same work after its post.)  Every wave then places its records at base + rank.
-// A record's staging position is c + (rstart -
-// rpre) of its run: the wave holds a window of 64 runs (a lane each), pushes one flag per run boundary to the lane
+// The loaders run one chunk further ahead than they place.  While the walkers walk chunk i, a loader wave
+// (`loader_iter`) takes its results of chunk i-1 out of the other LDS buffer into registers, decodes its records of
+// chunk i+1 (they were loaded during iteration i-1 and ranked at its end), issues the lookups and loads of chunk i+2
+// into the freed record registers, packs and stores the results, places chunk i+1 at base + rank, and last -- the
+// loads have had the store and the placement to arrive -- ranks chunk i+2 into its per-wave slot counters.  The
+// workgroup barrier that ends the iteration then orders the twelve waves' counters before the scan: at the top of
+// the next iteration ONE loader wave (a different one each chunk) turns them in place into placement bases (slot
+// start + the counts of the waves before, k_part_v4's wave-0 scan) and the walkers' slot starts, and posts on the
+// LDS counter `lbar`.  Nobody needs the bases before its placement, most of an iteration later, so the wait for the
+// post falls through: no loader wave waits for another in the steady state, and rank and slot of a record (one
+// packed register each) are the only ranking state that lives across the barrier.
+//
+// A record's staging position is c + (rstart - rpre) of its run: the wave holds a window of 64 runs (a lane each), pushes one flag per run boundary to the lane
 // the boundary falls on (ds_permute) and counts the flags at or below each lane (ballot + mbcnt); a window with an
 // empty run (two boundaries on one lane) or with more than 64 runs takes the per-wave search instead.
 // The workgroups of one XCD (blockIdx b and b + 8 share one) take a contiguous range of super-buckets (`s` below),
 // so the 128-byte lines two neighbouring super-buckets share at their run boundaries meet in one L2.
 //
-// LDS hazards (the chunk pipeline; cf. the k_apply_map chunk-0 race):
-//   * buffer b is placed by the loaders during iteration i-1 and walked during iteration i; the one workgroup
-//     barrier per iteration separates the two, and the walkers' in-place results in b are read back by the loaders
-//     only in iteration i+1 (after the next barrier);
-//   * those result reads (sab[b] at the top of `prepare`) come before the wave's arrival on lbar, and no wave places
-//     into sab[b] / sm[b] before the scanning wave's post, which follows all twelve arrivals: every result is in
-//     registers before its LDS word is overwritten;
-//   * wcnt (one buffer): a wave zeroes ITS OWN row at the top of `prepare` and ranks into it (one wave's LDS accesses
-//     stay in order).  The row's other accesses are the scanning wave's (read + rewritten between the twelve arrivals
-//     and its post) and the wave's own base reads at the placement (after the post, before the workgroup barrier);
-//     the next zeroing comes after that barrier;
-//   * sstart[b] is written by the scanning wave before the workgroup barrier and read by the walkers after it;
-//   * lbar only grows: 13 per chunk (twelve arrivals + the post); each wave counts the same targets in a register;
+// LDS hazards (the chunk pipeline; cf. the k_apply_map chunk-0 race).  B(i) is the workgroup barrier that
+// ends iteration i (the walk of chunk i); B(-2) and B(-1) are the prologue's two.  Loader iteration i places chunk
+// i+1; the prologue's (between B(-2) and B(-1), no walk beside it) is iteration -1 and places chunk 0.
+//   * buffer b = c & 1 is placed with chunk c during iteration c-1 and walked during iteration c; B(c-1) separates the
+//     two.  The walkers' in-place results in it are read back by the loaders in iteration c+1, after B(c);
+//   * those result reads (sab[b] at the top of `loader_iter`) must precede every wave's placement of chunk c+2 into
+//     the same buffer in the same iteration.  Nothing else orders two loader waves there any more, so each wave
+//     arrives on the LDS counter `rbar` once its results are in registers and waits for all twelve arrivals of the
+//     iteration before its first placement.  The arrivals are the first thing after the barrier and the placement
+//     comes after the decode, the lookups and the result store, so the wait falls through;
+//   * wcnt (one buffer).  Row w is zeroed and ranked by wave w alone, at the end of iteration i-1 (chunk i+1), after
+//     that wave's placement of chunk i has read the row's previous bases (one wave's LDS accesses stay in order);
+//     read and rewritten by the scanning wave at the top of iteration i, after B(i-1); read by wave w's placement of
+//     chunk i+1 after the post; zeroed again after that placement.  The scan of chunk i+2 comes after B(i);
+//   * sstart[c & 1] is written by chunk c's scan at the top of iteration c-1, while the walkers read sstart[(c-1) & 1];
+//     they read it at the top of iteration c, after B(c-1), and are done with chunk c-2's before B(c-2);
+//   * the counters only grow and every wave counts the same targets in a register: rbar by twelve per loader
+//     iteration (target 12, 24, ...: rd_n), lbar by one per chunk (the post of chunk c makes it c + 1).
+//     Prologue: every loader wave loads and ranks chunk 0; B(-2); iteration -1: wave 0 scans chunk 0 and posts
+//     (lbar = 1), all read dummy results, arrive (rbar = 12), load chunk 1, wait for rbar >= 12 and lbar >= 1 -- the
+//     one place where the post is really waited for -- place chunk 0 and rank chunk 1; B(-1).
+//     Steady state, iteration i = 0 .. nch-1: wave (i+1) % 12 scans chunk i+1 and posts (lbar = i + 2); all arrive
+//     (rbar = 12 (i + 2)), wait for both, place chunk i+1, rank chunk i+2; B(i).  The posts are one barrier apart,
+//     so lbar >= c + 1 means exactly "chunk c is scanned"; the scanning wave rotates with the chunk and wraps after
+//     twelve.  The chunks past the end (nch and nch + 1) are loaded from the dummy words, ranked, scanned and
+//     "placed" like any other with no live record, so no count depends on where the list ends.
+//     Epilogue: after B(nch-1) the loaders store the last chunk's results; no counter is touched.  At the end
+//     lbar = nch + 1 and rbar = 12 (nch + 1).
+//     nch = 0: the prologue alone (lbar = 1, rbar = 12), no walk.  nch = 1: the prologue and iteration 0, whose
+//     scan, placement and rank are of empty chunks.  nch = 2: chunk 1 is the last one placed with live records (in
+//     iteration 0).  nch >= 3: every role above is live.  No wait depends on anything but the workgroup-uniform
+//     iteration count, and every wait's arrivals precede a barrier the waiting wave has not reached yet;
 //   * rb0 / rpre (the run table) are written once, before the first workgroup barrier, and never rebuilt.
 constexpr int kWsPer = 4;
 // NS slots per super-bucket: 256 (1024-thread workgroups: 4 walker + 12 loader waves, 3072-record chunks, one
@@ -440,7 +463,7 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
   __shared__ uint16_t rb0[kV3MaxTiles];         // start of this super-bucket's run inside tile r
   __shared__ uint32_t rpre[kV3MaxTiles + 1];    // records of this super-bucket before tile r
   __shared__ uint32_t wsum[kAVW];
-  __shared__ uint32_t lbar;
+  __shared__ uint32_t lbar, rbar;               // the loaders' counters: chunks posted, result-read arrivals
   auto rstart = [&](uint32_t r) -> uint32_t { return r * kV3Tile + rb0[r]; };  // staging position of run r
 
   // Workgroups b and b + 8 share an XCD (observed dispatch; speed only, any placement gives the same results):
@@ -457,7 +480,7 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
     ms = val_meta[(uint64_t)s * kVSlots3 + t];
     sv = val_v[(uint64_t)s * kVSlots3 + t];
   }
-  if (t == 0) lbar = 0;  // (wcnt: every loader wave zeroes its row before it ranks)
+  if (t == 0) lbar = rbar = 0;  // (wcnt: every loader wave zeroes its row before it ranks)
   {  // the super-bucket's list = its run in every tile, in tile order; thread t owns tiles TPT*t .. TPT*t + TPT-1
     uint32_t len[P::TPT], lsum = 0;
 #pragma unroll
@@ -498,8 +521,8 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
   const uint32_t nch = (cnt + kWsCh - 1) / kWsCh;
   uint32_t err = 0, macc = 0;  // macc: OR of the meta words this thread walked
 #ifdef CC_PHASE_TIMING
-  // thread 0 (walker): 0 walk, 1 wait; thread 256 (loader): 2 result store, 3 rank, 4 loader + workgroup barriers,
-  // 5 clear + placement bases, 6 decode + place, 7 load issue
+  // thread 0 (walker): 0 walk, 1 wait; thread 256 (loader): 2 result store, 3 clear + rank (with the wait for the
+  // loads), 4 counter waits + workgroup barriers, 5 placement bases, 6 result reads + decode + place, 7 load issue
   uint64_t wph_last = wall_clock64(), wph[kPhases] = {0, 0, 0, 0, 0, 0, 0, 0};
   auto WPH = [&](int k) {
     if (t == 0 || t == kL0) {
@@ -512,8 +535,9 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
   auto WPH = [&](int) {};
 #endif
 
-  // loader registers: the chunk to place next (rr, g; loaded one chunk ahead), the sorted / staging positions of the
-  // chunk being walked (pp, gp) and of the chunk before it (qp, gq: its results are stored during the walk)
+  // loader registers: the chunk to place next (rr, g; loaded and ranked one iteration ahead), the sorted / staging
+  // positions of the chunk being walked (pp, gp) and of the chunk before it (qp, gq: its results are stored during
+  // the walk)
 #define CC_J4(X) X(0) X(1) X(2) X(3)
   // A record past the end of the list has the staging position dpos, one of the dummy words behind the staging area
   // (its loads and result stores stay unconditional): a position is live iff it is below dpos0.
@@ -570,7 +594,9 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
     }                                                                                             \
     CC_J4(CC_LOAD1)                                                                               \
   }
-  uint32_t bar_n = 0;  // the loaders' counter (lbar) after the previous chunk
+  uint32_t rd_n = 0;  // rbar after the previous loader iteration (twelve result-read arrivals each)
+  // the registers' chunk as ranked at the end of the iteration before: rank (< 3072) | slot << 16
+  uint32_t rs0 = 0, rs1 = 0, rs2 = 0, rs3 = 0;
   // the results of the chunk walked before (buffer b, positions qp / gq) into registers, ahead of the placement that
   // overwrites them; then over the records themselves at their staging positions (each record is read once, by this
   // workgroup, a chunk earlier): one packed word per result (v3_pack_result), unconditional stores (rows past the
@@ -589,74 +615,72 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
     }                                                                               \
     st_rec[gq##J] = wd_;                                                            \
   }
-  // One chunk's loader work: the results of chunk i-1 out of buffer b, then the registers' chunk (i+1) ranked and
-  // placed into buffer b; loader wave scan_w turns the counters into the placement bases for all.
-  auto prepare = [&](uint32_t b, uint32_t scan_w, uint32_t next_c0) {
-    CC_J4(CC_RES_READ)
+  // Rank the registers' chunk into this wave's counter row (the last thing a loader wave does before a workgroup
+  // barrier: the barrier, not a counter, orders the twelve rows before the scan that follows it).
+  auto rank_chunk = [&]() {
     for (uint32_t k = l; k < (uint32_t)kVPairs3; k += kWave) wcnt[lw][k] = 0;
-    uint32_t rank[kWsPer], slot[kWsPer];
-    const uint64_t rv4[kWsPer] = {rr0, rr1, rr2, rr3};
-    const uint32_t gv[kWsPer] = {g0, g1, g2, g3};
-#pragma unroll
-    for (int j = 0; j < kWsPer; ++j) {
-      slot[j] = v3_slot(rv4[j]);
-      const uint32_t sh = 16 * (slot[j] & 1);
-      rank[j] = gv[j] < dpos0 ? (atomicAdd(&wcnt[lw][slot[j] >> 1], 1u << sh) >> sh) & 0xFFFFu : 0u;
+#define CC_RANK1(J)                                                                 \
+    {                                                                               \
+      const uint32_t sl_ = v3_slot(rr##J), sh_ = 16 * (sl_ & 1);                    \
+      const uint32_t rk_ = g##J < dpos0 ? (atomicAdd(&wcnt[lw][sl_ >> 1], 1u << sh_) >> sh_) & 0xFFFFu : 0u; \
+      rs##J = rk_ | (sl_ << 16);                                                    \
     }
+    CC_J4(CC_RANK1)
+#undef CC_RANK1
     WPH(3);
-    v3_loader_arrive(&lbar);  // this wave has ranked the chunk, and has chunk i-1's results in registers
-    if (lw == scan_w) {       // wave-uniform
-      v3_loader_wait(&lbar, bar_n + kWsLW);  // every loader wave has arrived
-      WPH(4);
-      // lane l owns slots SPL*l .. SPL*l + SPL-1 (counter pairs PPL*l ..): the slots' totals over the waves, their
-      // exclusive scan (the slot starts), then each wave's counter replaced by start + the counts of the waves before
-      constexpr int PPL = P::SPL / 2;
-      uint32_t acc[PPL], mine = 0;
+  };
+  // One loader wave per chunk (c % 12, at the top of the iteration that places chunk c) turns the twelve rows into
+  // chunk c's placement bases and the walkers' sstart[b] (b = c & 1), and posts: lbar = chunks posted.
+  auto scan_chunk = [&](uint32_t b) {
+    // lane l owns slots SPL*l .. SPL*l + SPL-1 (counter pairs PPL*l ..): the slots' totals over the waves, their
+    // exclusive scan (the slot starts), then each wave's counter replaced by start + the counts of the waves before
+    constexpr int PPL = P::SPL / 2;
+    uint32_t acc[PPL], mine = 0;
 #pragma unroll
-      for (int e = 0; e < PPL; ++e) acc[e] = 0;
+    for (int e = 0; e < PPL; ++e) acc[e] = 0;
 #pragma unroll
-      for (int q = 0; q < kWsLW; ++q) {
+    for (int q = 0; q < kWsLW; ++q) {
 #pragma unroll
-        for (int e = 0; e < PPL; ++e) acc[e] += wcnt[q][PPL * l + e];
-      }
+      for (int e = 0; e < PPL; ++e) acc[e] += wcnt[q][PPL * l + e];
+    }
 #pragma unroll
-      for (int e = 0; e < PPL; ++e) mine += (acc[e] & 0xFFFFu) + (acc[e] >> 16);
-      uint32_t inc = mine;
+    for (int e = 0; e < PPL; ++e) mine += (acc[e] & 0xFFFFu) + (acc[e] >> 16);
+    uint32_t inc = mine;
 #pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(inc, d, 64);
-        if (l >= (uint32_t)d) inc += y;
-      }
-      uint32_t run = inc - mine;
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t y = __shfl_up(inc, d, 64);
+      if (l >= (uint32_t)d) inc += y;
+    }
+    uint32_t run = inc - mine;
+#pragma unroll
+    for (int e = 0; e < PPL; ++e) {
+      const uint32_t k = P::SPL * l + 2 * e;
+      const uint32_t lo_ = run, hi_ = run + (acc[e] & 0xFFFFu);
+      sstart[b][k] = lo_;  // the walkers' run starts of chunk c (read after the next workgroup barrier)
+      sstart[b][k + 1] = hi_;
+      run = hi_ + (acc[e] >> 16);
+      acc[e] = lo_ | (hi_ << 16);
+    }
+    if (l == 63) sstart[b][kVSlots3] = inc;
+#pragma unroll
+    for (int q = 0; q < kWsLW; ++q) {
 #pragma unroll
       for (int e = 0; e < PPL; ++e) {
-        const uint32_t k = P::SPL * l + 2 * e;
-        const uint32_t lo_ = run, hi_ = run + (acc[e] & 0xFFFFu);
-        sstart[b][k] = lo_;  // the walkers' run starts (read after the workgroup barrier)
-        sstart[b][k + 1] = hi_;
-        run = hi_ + (acc[e] >> 16);
-        acc[e] = lo_ | (hi_ << 16);
+        const uint32_t cv = wcnt[q][PPL * l + e];
+        wcnt[q][PPL * l + e] = acc[e];
+        acc[e] += cv;  // no carry between the halves: every sum is a position <= 3072
       }
-      if (l == 63) sstart[b][kVSlots3] = inc;
-#pragma unroll
-      for (int q = 0; q < kWsLW; ++q) {
-#pragma unroll
-        for (int e = 0; e < PPL; ++e) {
-          const uint32_t cv = wcnt[q][PPL * l + e];
-          wcnt[q][PPL * l + e] = acc[e];
-          acc[e] += cv;  // no carry between the halves: every sum is a position <= 3072
-        }
-      }
-      WPH(5);
-      v3_loader_arrive(&lbar);  // the post: the bases are in wcnt
     }
-    bar_n += kWsLW + 1;
-    CC_J4(CC_RES_WRITE)
-    WPH(2);
-#define CC_SHIFT1(J) qp##J = pp##J; gq##J = gp##J;
-    CC_J4(CC_SHIFT1)
-#undef CC_SHIFT1
-    // the decode does not need the bases: it runs while the scanning wave works
+    WPH(5);
+    v3_loader_arrive(&lbar);  // the post: chunk c's bases are in wcnt
+  };
+  // One loader iteration, beside the walk of chunk c-1: chunk c's scan (one wave), the results of chunk c-2 out of
+  // buffer b = c & 1, the registers' chunk c (ranked before the last barrier, rs) decoded and placed into buffer b,
+  // chunk c+1 loaded into the freed registers and ranked.
+  auto loader_iter = [&](uint32_t c, uint32_t b) {
+    if (lw == c % (uint32_t)kWsLW) scan_chunk(b);  // wave-uniform
+    CC_J4(CC_RES_READ)
+    v3_loader_arrive(&rbar);  // chunk c-2's results of this wave are in registers
 #define CC_DEC1(J)                                                                  \
     const bool live##J = g##J < dpos0;                                              \
     uint32_t m##J;                                                                  \
@@ -669,18 +693,26 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
     CC_J4(CC_DEC1)
 #undef CC_DEC1
     WPH(6);
-    // nor do the position lookups and the loads of the chunk after: the registers' records are decoded
-#define CC_KEEP1(J) gp##J = g##J;
+    // the records are decoded: their registers take chunk c+1 (lookups, then the loads; the result store and the
+    // placement below run while the loads are in flight)
+#define CC_KEEP1(J) const uint32_t gc##J = g##J;
     CC_J4(CC_KEEP1)
 #undef CC_KEEP1
-    CC_LOAD_CHUNK(next_c0)
+    CC_LOAD_CHUNK((c + 1) * (uint32_t)kWsCh)
     WPH(7);
-    v3_loader_wait(&lbar, bar_n);  // the scanning wave's post (every loader wave waits, the scanning one for itself)
+    CC_J4(CC_RES_WRITE)
+    WPH(2);
+#define CC_SHIFT1(J) qp##J = pp##J; gq##J = gp##J; gp##J = gc##J;
+    CC_J4(CC_SHIFT1)
+#undef CC_SHIFT1
+    rd_n += kWsLW;
+    v3_loader_wait(&rbar, rd_n);      // every loader wave holds its results of chunk c-2: buffer b may be overwritten
+    v3_loader_wait(&lbar, c + 1);     // chunk c's bases are posted (at the top of this iteration)
     WPH(4);
     const uint16_t* pb = reinterpret_cast<const uint16_t*>(&wcnt[lw][0]);  // u16 half k = slot k (little endian)
 #define CC_PLACE1(J)                                                                \
     {                                                                               \
-      pp##J = live##J ? pb[slot[J]] + rank[J] : 0u;                                 \
+      pp##J = live##J ? pb[rs##J >> 16] + (rs##J & 0xFFFFu) : 0u;                   \
       if (live##J) {                                                                \
         sm[b][pp##J] = m##J;                                                        \
         sab[b][pp##J] = u64x2{x##J, y##J};                                          \
@@ -689,12 +721,15 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
     CC_J4(CC_PLACE1)
 #undef CC_PLACE1
     WPH(6);
+    rank_chunk();  // chunk c+1 (waits for its loads)
   };
 
-  if (!walker) {
+  if (!walker) {  // prologue: chunk 0 loaded and ranked; then one loader iteration without a walk
     CC_LOAD_CHUNK(0)
-    prepare(0, 0, kWsCh);
+    rank_chunk();
   }
+  lds_barrier();
+  if (!walker) loader_iter(0, 0);  // chunk 0 scanned and placed, chunk 1 loaded and ranked
   lds_barrier();
   for (uint32_t i = 0; i < nch; ++i) {
     const uint32_t b = i & 1;
@@ -736,8 +771,9 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
         }
       }
     } else {
-      // chunk i-1's results (i = 0: the dummy rows), chunk i+1's placement (past the end: no live records)
-      prepare(b ^ 1, (i + 1) % (uint32_t)kWsLW, (i + 2) * kWsCh);
+      // chunk i-1's results (i = 0: the dummy rows), chunk i+1's scan and placement (past the end: no live records),
+      // chunk i+2's loads and rank (past the end: empty)
+      loader_iter(i + 1, b ^ 1);
     }
     if (walker) WPH(0);
     lds_barrier();  // buffer hand-over: b walked (results in place), b^1 placed
