@@ -1,5 +1,5 @@
-// engine.hip — the C-ABI of include/copycat_apply.h: engine handle, resource/instance registry, and the
-// batched apply driver (partition.hip -> apply_*.hip per sub-batch).
+// engine.hip — the C-ABI of include/copycat_apply.h: engine handle, resource/instance registry, readback,
+// snapshots.  The batched apply driver (cc_apply_batch) is apply_batch.hip.
 //
 // Reference interface replaced: the Copycat StateMachine that ResourceManager implements
 // (manager/src/main/java/io/atomix/manager/ResourceManager.java:35-264), applying committed entries
@@ -68,7 +68,7 @@ static void mark_fn(void* ctx, int k, int begin, hipStream_t st) {
   }
 }
 
-static Marker marker_of(cc_engine* e) { return Marker{e->prof_on ? &mark_fn : nullptr, e}; }
+Marker cc::marker_of(cc_engine* e) { return Marker{e->prof_on ? &mark_fn : nullptr, e}; }
 
 static void drain_profile(cc_engine* e) {
   for (auto& p : e->pending) {
@@ -98,12 +98,12 @@ static void free_all(cc_engine* e) {
                   e->d_tbl_dl,   e->d_map_row,  e->d_ttl_seen, e->d_val_live, e->d_val_wrow,
                   e->d_leak,     e->d_leak_n,   e->d_ev_bucket, e->d_ev_ccnt, e->d_rst_msz, e->d_hot_msz, e->d_msize,
                   e->d_mpcap,    e->d_msz_tcnt, e->d_msz_list, e->d_msz_list_n, e->d_msm,     e->d_mbig,     e->d_msmall,  e->d_msm_left, e->d_span_cut,
-                  e->d_sm_ctl,   e->d_sm_key,   e->d_sm_key2,  e->d_sm_val,   e->d_sm_val2,    e->d_sm_seg, e->d_sm_temp, e->d_sm_pay,
+                  e->d_sm_ctl,   e->d_sm_seg,   e->d_sm_temp,
                   e->d_szq,      e->d_szq_n,    e->d_mrec,    e->d_bar_rows, e->d_fb,
                   e->d_cvq,      e->d_cvq_n,    e->d_isc,     e->d_isc2,     e->d_mfirst,     e->d_maynull, e->d_cv_rtemp,
                   e->d_cvset,    e->d_cvcnt,    e->d_cvev_key, e->d_cvev_key2, e->d_cvev_val, e->d_cvev_val2, e->d_cvev_ctl,
                   e->d_cvseg,    e->d_cvtemp,   e->d_clrq,    e->d_clrq_n,   e->d_clr_keys,   e->d_clr_keys2, e->d_clr_off,
-                  e->d_clr_base, e->d_clr_eend, e->d_clr_temp, e->d_tbl_ep, e->d_clr_scan, e->d_clr_stemp, e->d_clr_btab, e->d_sm_cseg, e->d_cvbloom,
+                  e->d_clr_base, e->d_clr_eend, e->d_clr_temp, e->d_tbl_ep, e->d_clr_scan, e->d_clr_stemp, e->d_clr_btab, e->d_cvbloom,
                   e->d_px,       e->d_px_bcnt,  e->d_px_evn};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -114,9 +114,8 @@ static void free_all(cc_engine* e) {
   if (e->h_pin) (void)hipHostFree(e->h_pin);
   if (e->d_ckpt) (void)hipFree(e->d_ckpt);
   if (e->side_st) (void)hipStreamSynchronize(e->side_st);
-  void* alt[] = {e->sm_alt.key, e->sm_alt.key2, e->sm_alt.val, e->sm_alt.val2, e->sm_alt.pay, e->sm_alt.cseg};
-  for (void* p : alt)
-    if (p) (void)hipFree(p);
+  e->sm.release();
+  e->sm_alt.release();
   for (hipEvent_t ev : {e->ev_prep, e->ev_rep[0], e->ev_rep[1], e->ev_rb})
     if (ev) (void)hipEventDestroy(ev);
   if (e->side_st) (void)hipStreamDestroy(e->side_st);
@@ -126,225 +125,16 @@ static void free_all(cc_engine* e) {
 constexpr uint64_t kLeakCap = 1u << 20;  // leak log entries between drains (16 MiB)
 
 // The leak log with room for `need` entries past those already drained (an empty log is reallocated).
-static int ensure_leak(cc_engine* e, uint64_t need) {
+int cc::ensure_leak(cc_engine* e, uint64_t need) {
   if (!e->d_leak_n) {
     hipError_t x = hipMalloc(&e->d_leak_n, sizeof(unsigned long long));
     if (x == hipSuccess) x = hipMemset(e->d_leak_n, 0, sizeof(unsigned long long));
     if (x != hipSuccess) return set_err(CC_ERR_HIP, "leak log counter", x);
   }
   if (e->d_leak && e->leak_cap >= need) return CC_OK;
-  if (e->d_leak) {
-    int rc = drain_leaks(e);
-    if (rc) return rc;
-    (void)hipFree(e->d_leak);
-    e->d_leak = nullptr;
-  }
+  if (e->d_leak) TRY(drain_leaks(e));
   const uint64_t cap = std::max<uint64_t>(need, kLeakCap);
-  hipError_t x = hipMalloc(&e->d_leak, sizeof(LeakRec) * cap);
-  if (x != hipSuccess) return set_err(CC_ERR_HIP, "hipMalloc leak log", x);
-  e->leak_cap = cap;
-  return CC_OK;
-}
-
-// The map event buffers (map_small.hip), sorted by hipcub: one event per map commit of a sub-batch at most; in TTL
-// mode also one per expiry (at most one per commit that sees its key's timer fired, plus one per table entry).
-static uint64_t small_cap_needed(const cc_engine* e) {
-  return e->ttl_live ? 2 * e->sub_batch + e->map_entries : e->sub_batch;
-}
-static int launch_pending_replay(cc_engine* e, hipStream_t st);
-static int wait_replay(cc_engine* e, int k, hipStream_t st);
-static void free_sm_alt(cc_engine* e) {
-  // (inside a batch: a replay not yet launched runs now, and every replay's exit marks fold into the snapshot on the
-  // engine stream -- e->last_stream -- before the buffers go)
-  if (e->last_stream) {
-    (void)launch_pending_replay(e, e->last_stream);
-    for (int k = 0; k < 2; ++k) (void)wait_replay(e, k, e->last_stream);
-    (void)hipStreamSynchronize(e->last_stream);
-  }
-  if (e->side_st) (void)hipStreamSynchronize(e->side_st);
-  e->rep_pending[0] = e->rep_pending[1] = false;
-  void* alt[] = {e->sm_alt.key, e->sm_alt.key2, e->sm_alt.val, e->sm_alt.val2, e->sm_alt.pay, e->sm_alt.cseg};
-  for (void* p : alt)
-    if (p) (void)hipFree(p);
-  e->sm_alt = cc_engine::SmSet{};
-  e->sm_alt_on = false;
-}
-static int ensure_small(cc_engine* e) {
-  const uint64_t cap = small_cap_needed(e);
-  if (e->d_sm_key && e->sm_cap >= cap) return CC_OK;
-  if (cap > 0xFFFFFFFFull) return set_err(CC_ERR_CAPACITY, "map event buffer beyond 2^32 entries");
-  if (e->d_sm_key) {  // grown (TTL mode): the counters keep their buffer, the events are rebuilt per sub-batch
-    free_sm_alt(e);  // (the side stream's replay is done with either set)
-    void* ps[] = {e->d_sm_key, e->d_sm_key2, e->d_sm_val, e->d_sm_val2, e->d_sm_temp, e->d_sm_pay};
-    for (void* p : ps) (void)hipFree(p);
-    e->d_sm_key = e->d_sm_key2 = nullptr;
-    e->d_sm_val = e->d_sm_val2 = nullptr;
-    e->d_sm_pay = nullptr;
-    e->d_sm_temp = nullptr;
-  }
-  const size_t tb = std::max<size_t>(small_sort_temp_bytes((uint32_t)cap), 256);
-  hipError_t x = hipMalloc(&e->d_sm_key, 8 * cap);
-  if (x == hipSuccess) x = hipMalloc(&e->d_sm_key2, 8 * cap);
-  if (x == hipSuccess) x = hipMalloc(&e->d_sm_val, 4 * cap);
-  if (x == hipSuccess) x = hipMalloc(&e->d_sm_val2, 4 * cap);
-  if (x == hipSuccess) x = hipMalloc(&e->d_sm_pay, sizeof(EvPay) * cap);
-  if (x == hipSuccess && !e->d_sm_seg) x = hipMalloc(&e->d_sm_seg, 4ull * (e->cfg.max_resources + 1));
-  if (x == hipSuccess && !e->d_sm_cseg) x = hipMalloc(&e->d_sm_cseg, 4ull * (e->cfg.max_resources + 2));
-  if (x == hipSuccess) x = hipMalloc(&e->d_sm_temp, tb);
-  if (x != hipSuccess) return set_err(CC_ERR_HIP, "hipMalloc map events", x);
-  e->sm_temp_bytes = tb;
-  e->sm_cap = cap;
-  return CC_OK;
-}
-// the second event-buffer set and the side stream of the overlapped small-map replay (engine_state.h SmSet)
-static int ensure_sm_alt(cc_engine* e) {
-  if (e->sm_alt_on) return CC_OK;
-  const uint64_t cap = e->sm_cap;
-  hipError_t x = hipSuccess;
-  if (!e->side_st) x = hipStreamCreateWithFlags(&e->side_st, hipStreamNonBlocking);
-  for (hipEvent_t* ev : {&e->ev_prep, &e->ev_rep[0], &e->ev_rep[1]})
-    if (x == hipSuccess && !*ev) x = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-  if (x == hipSuccess) x = hipMalloc(&e->sm_alt.key, 8 * cap);
-  if (x == hipSuccess) x = hipMalloc(&e->sm_alt.key2, 8 * cap);
-  if (x == hipSuccess) x = hipMalloc(&e->sm_alt.val, 4 * cap);
-  if (x == hipSuccess) x = hipMalloc(&e->sm_alt.val2, 4 * cap);
-  if (x == hipSuccess) x = hipMalloc(&e->sm_alt.pay, sizeof(EvPay) * cap);
-  if (x == hipSuccess) x = hipMalloc(&e->sm_alt.cseg, 4ull * (e->cfg.max_resources + 2));
-  if (x != hipSuccess) return set_err(CC_ERR_HIP, "hipMalloc map events (second set)", x);
-  e->sm_alt_on = true;
-  return CC_OK;
-}
-// the deferred replay on the side stream, after what the engine stream has queued so far
-static int launch_pending_replay(cc_engine* e, hipStream_t st) {
-  if (!e->pend) return CC_OK;
-  e->pend = false;
-  HIPCHECK(hipEventRecord(e->ev_prep, st));
-  HIPCHECK(hipStreamWaitEvent(e->side_st, e->ev_prep, 0));
-  if (launch_small_replay_kernel(e->pend_sa, e->side_st)) return set_err(CC_ERR_HIP, "small-map replay launch", hipGetLastError());
-  HIPCHECK(hipEventRecord(e->ev_rep[e->pend_set], e->side_st));
-  e->rep_pending[e->pend_set] = true;
-  return CC_OK;
-}
-// the engine stream waits for the side-stream replay of event-buffer set k, then folds its exit marks into the
-// d_msmall snapshot (common.h, the small-map window invariant: the only place a replay's result reaches the flags)
-static int wait_replay(cc_engine* e, int k, hipStream_t st) {
-  if (!e->rep_pending[k]) return CC_OK;
-  HIPCHECK(hipStreamWaitEvent(st, e->ev_rep[k], 0));
-  e->rep_pending[k] = false;
-  if (launch_small_fold(e->d_msm_left + (size_t)k * e->cfg.max_resources, e->d_msmall, e->cfg.max_resources, st))
-    return set_err(CC_ERR_HIP, "small-map fold launch", hipGetLastError());
-  return CC_OK;
-}
-// the engine stream waits for the side stream's replays (before barrier rows, timers, and the batch's end)
-static int join_replay(cc_engine* e, hipStream_t st) {
-  {
-    int rc = launch_pending_replay(e, st);
-    if (rc) return rc;
-  }
-  for (int k = 0; k < 2; ++k) {
-    int rc = wait_replay(e, k, st);
-    if (rc) return rc;
-  }
-  return CC_OK;
-}
-
-// the cleared maps' size scan (map_clear.hip): one element per map event, sized with the event buffer
-static int ensure_clr_scan(cc_engine* e) {
-  if (e->d_clr_scan && e->clr_scan_cap >= e->sm_cap) return CC_OK;
-  if (e->d_clr_scan) (void)hipFree(e->d_clr_scan);
-  if (e->d_clr_stemp) (void)hipFree(e->d_clr_stemp);
-  e->d_clr_scan = e->d_clr_stemp = nullptr;
-  const size_t tb = std::max<size_t>(clr_scan_temp_bytes((uint32_t)e->sm_cap), 256);
-  hipError_t x = hipMalloc(&e->d_clr_scan, clr_scan_bytes_per_event() * e->sm_cap);
-  if (x == hipSuccess) x = hipMalloc(&e->d_clr_stemp, tb);
-  if (x != hipSuccess) return set_err(CC_ERR_HIP, "hipMalloc clear size scan", x);
-  e->clr_scan_cap = e->sm_cap;
-  e->clr_stemp_bytes = tb;
-  return CC_OK;
-}
-
-// containsValue in the stream (map_cv.hip): the batch's in-stream rows sorted (device) and copied to the host, which
-// cuts each sub-batch's slice of them.
-constexpr uint32_t kCvMaxRows = 1u << 21;  // in-stream containsValue rows per sub-batch (a denser run shortens it)
-static int cv_rows(cc_engine* e, uint32_t n2, hipStream_t st) {
-  e->isc_rows.clear();
-  if (n2 == 0) return CC_OK;
-  const size_t need = std::max<size_t>(cv_rows_temp_bytes(e->cvq_cap), 256);
-  if (!e->d_isc2 || need > e->cv_rtemp_bytes) {
-    if (e->d_isc2) HIPCHECK(hipFree(e->d_isc2));
-    if (e->d_cv_rtemp) HIPCHECK(hipFree(e->d_cv_rtemp));
-    e->d_isc2 = nullptr;
-    e->d_cv_rtemp = nullptr;
-    HIPCHECK(hipMalloc(&e->d_isc2, sizeof(uint32_t) * e->cvq_cap));
-    HIPCHECK(hipMalloc(&e->d_cv_rtemp, need));
-    e->cv_rtemp_bytes = need;
-  }
-  if (cv_sort_rows(e->d_isc, e->d_isc2, n2, e->d_cv_rtemp, e->cv_rtemp_bytes, st))
-    return set_err(CC_ERR_HIP, "containsValue row sort", hipGetLastError());
-  e->isc_rows.resize(n2);
-  HIPCHECK(hipMemcpyAsync(e->isc_rows.data(), e->d_isc2, sizeof(uint32_t) * n2, hipMemcpyDeviceToHost, st));
-  HIPCHECK(hipStreamSynchronize(st));
-  return CC_OK;
-}
-// clears in the stream (map_clear.hip): the batch's list sorted by (map, row) with per-map offsets on the device; the
-// host keeps the rows of any map cleared 128 times or more (a sub-batch holds at most 127 clears of one map)
-static int clr_rows(cc_engine* e, uint32_t n, const cc_batch* c, hipStream_t st) {
-  e->clr_n = n;
-  e->clr_heavy.clear();
-  if (n == 0) return CC_OK;
-  ClrBatchArgs cb{};
-  cb.rows = e->d_clrq;
-  cb.n = n;
-  cb.inst = c->inst;
-  cb.inst_res = e->d_inst_res;
-  cb.keys = e->d_clr_keys;
-  cb.keys2 = e->d_clr_keys2;
-  cb.off = e->d_clr_off;
-  cb.R = e->cfg.max_resources;
-  cb.temp = e->d_clr_temp;
-  cb.temp_bytes = e->clr_temp_bytes;
-  if (launch_clr_batch(cb, st)) return set_err(CC_ERR_HIP, "clear list launch", hipGetLastError());
-  if (n >= 128) {
-    std::vector<uint64_t> keys(n);
-    HIPCHECK(hipMemcpyAsync(keys.data(), e->d_clr_keys2, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    for (uint32_t a = 0; a < n;) {
-      uint32_t b = a;
-      while (b < n && (keys[b] >> 32) == (keys[a] >> 32)) ++b;
-      if (b - a >= 128) {
-        std::vector<uint32_t> rows(b - a);
-        for (uint32_t q = a; q < b; ++q) rows[q - a] = (uint32_t)keys[q];
-        e->clr_heavy.push_back(std::move(rows));
-      }
-      a = b;
-    }
-  }
-  return CC_OK;
-}
-
-// the operand set (sized for kCvMaxRows operands) and the event buffers (two events per commit, one per query)
-constexpr uint32_t kCvBloomMaxBits = 25;  // the operand filter: ~16 bits per operand, 2^16 .. 2^25 bits
-static int ensure_cv(cc_engine* e) {
-  if (e->d_cvset) return CC_OK;
-  const uint32_t sc = 2 * kCvMaxRows;
-  const uint64_t ec = 2ull * e->sub_batch + kCvMaxRows;
-  if (ec > 0xFFFFFFFFull) return set_err(CC_ERR_CAPACITY, "containsValue event buffer beyond 2^32 entries");
-  const size_t tb = std::max<size_t>(cv_sort_temp_bytes((uint32_t)ec), 256);
-  hipError_t x = hipMalloc(&e->d_cvset, sizeof(CvEnt) * sc);
-  if (x == hipSuccess) x = hipMalloc(&e->d_cvcnt, sizeof(uint32_t) * sc);
-  if (x == hipSuccess) x = hipMalloc(&e->d_cvseg, sizeof(uint32_t) * (sc + 1));
-  if (x == hipSuccess) x = hipMalloc(&e->d_cvev_key, 8 * ec);
-  if (x == hipSuccess) x = hipMalloc(&e->d_cvev_key2, 8 * ec);
-  if (x == hipSuccess) x = hipMalloc(&e->d_cvev_val, 4 * ec);
-  if (x == hipSuccess) x = hipMalloc(&e->d_cvev_val2, 4 * ec);
-  if (x == hipSuccess) x = hipMalloc(&e->d_cvev_ctl, sizeof(uint32_t) * 2);
-  if (x == hipSuccess) x = hipMalloc(&e->d_cvtemp, tb);
-  if (x == hipSuccess) x = hipMalloc(&e->d_cvbloom, (1ull << kCvBloomMaxBits) / 8);
-  if (x != hipSuccess) return set_err(CC_ERR_HIP, "hipMalloc containsValue buffers", x);
-  e->cvset_cap = sc;
-  e->cvev_cap = (uint32_t)ec;
-  e->cvtemp_bytes = tb;
-  return CC_OK;
+  return regrow({BUF(e->d_leak, sizeof(LeakRec) * cap)}, e->leak_cap, cap, "hipMalloc leak log");
 }
 
 // Extended staging columns (maps, coordination, value events); with `coord`, the coordination blocks and the
@@ -953,1197 +743,6 @@ extern "C" int cc_instance_open_range(cc_engine* e, uint32_t first, uint32_t cou
                                       uint64_t client_session) {
   if (!e) return CC_ERR_INVALID;
   return open_range(e, first, count, res_first, 1, id_first, client_session);
-}
-
-// Diagnostics (CC_DEBUG_SYNC=1): drain the stream after every launch of cc_apply_batch and name the launch whose
-// kernels failed.
-static const bool g_dbg_sync = getenv("CC_DEBUG_SYNC") != nullptr;
-#define DBG_SYNC(what)                                                                          \
-  do {                                                                                          \
-    if (g_dbg_sync) {                                                                           \
-      hipError_t _x = hipStreamSynchronize(st);                                                 \
-      if (_x != hipSuccess) return set_err(CC_ERR_HIP, "CC_DEBUG_SYNC after " what, _x);        \
-    }                                                                                           \
-  } while (0)
-
-// TTL mode: the map events appended so far (commits, expiries) -> every map's size and capacity, the small maps' key
-// sets (map_small.hip: sort, runs, k_small_replay + k_ttl_replay), then the counters for the next round.
-static int ttl_replay(cc_engine* e, hipStream_t st, const uint64_t* index = nullptr, uint64_t lo = 0,
-                      const cc_results* out = nullptr) {
-  uint32_t ctl[2] = {0, 0};
-  HIPCHECK(hipMemcpyAsync(ctl, e->d_sm_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-  HIPCHECK(hipStreamSynchronize(st));
-  SmallArgs sa{};
-  sa.ev_key = e->d_sm_key;
-  sa.ev_key2 = e->d_sm_key2;
-  sa.ev_val = e->d_sm_val;
-  sa.ev_val2 = e->d_sm_val2;
-  sa.ev_pay = e->d_sm_pay;
-  sa.cap = (uint32_t)e->sm_cap;
-  sa.temp = e->d_sm_temp;
-  sa.temp_bytes = e->sm_temp_bytes;
-  sa.ctl = e->d_sm_ctl;
-  sa.seg = e->d_sm_seg;
-  sa.nseg = e->d_sm_seg + e->cfg.max_resources;
-  sa.state = e->d_msm;
-  sa.big = e->d_mbig;
-  sa.msmall = e->d_msmall;
-  sa.left = e->d_msm_left + 2ull * e->cfg.max_resources;  // (an engine-stream replay: folded right after it)
-  sa.err = e->d_err;
-  sa.mpcap = e->d_mpcap;
-  sa.max_resources = e->cfg.max_resources;
-  sa.msize = e->d_msize;
-  sa.lvl_at = e->d_lvl_at;
-  sa.index = index;  // (null for the expiry-only flushes: they grow no table)
-  sa.lo = lo;
-  sa.out_status = out ? out->status : nullptr;  // (the sub-batch's size / isEmpty rows among the events)
-  sa.out_value = out ? out->value : nullptr;
-  {
-    int rc = join_replay(e, st);  // (an overlapped replay of an earlier sub-batch: the models it writes)
-    if (rc) return rc;
-  }
-  const int rs = launch_small_replay(sa, ctl[0], st, st);
-  if (rs) return rs == -1 ? set_err(CC_ERR_HIP, "TTL map events launch", hipGetLastError())
-                          : set_err(CC_ERR_STATE, "TTL map events exceed their buffer");
-  if (launch_small_finish(sa, st)) return set_err(CC_ERR_HIP, "map event counters", hipGetLastError());
-  return CC_OK;
-}
-
-static TtlEmit ttl_emit_args(const cc_engine* e, const uint64_t* time, uint64_t n, uint64_t lo, uint64_t bl, uint64_t bh,
-                             uint64_t adv) {
-  TtlEmit t{};
-  t.time = time;
-  t.n = n;
-  t.lo = lo;
-  t.bl = bl;
-  t.bh = bh;
-  t.adv = adv;
-  t.deferred = (e->cfg.flags & CC_CFG_TIMERS_DEFERRED) ? 1u : 0u;
-  t.hh_key = e->d_hh_key;
-  t.hh_val = e->d_hh_val;
-  t.hh_n = e->hh_n;
-  t.ev_key = e->d_sm_key;
-  t.ev_val = e->d_sm_val;
-  t.ev_pay = e->d_sm_pay;
-  t.ev_cap = (uint32_t)e->sm_cap;
-  t.ctl = e->d_sm_ctl;
-  return t;
-}
-
-// TTL mode: the expiries of the boundaries [bl, bh] that no sub-batch owned (before a barrier row, at the batch end),
-// or every timer due by `adv` (cc_advance_time), as size events.
-static int ttl_flush(cc_engine* e, const uint64_t* time, uint64_t n, uint64_t bl, uint64_t bh, uint64_t adv,
-                     hipStream_t st) {
-  int rc = ensure_small(e);
-  if (rc) return rc;
-  const TtlEmit te = ttl_emit_args(e, time, n, bl, bl, bh, adv);
-  if (launch_ttl_scan(te, e->d_clock, e->d_tbl_word, e->d_tbl_key, e->d_tbl_dl, e->map_entries, e->d_err, st))
-    return set_err(CC_ERR_HIP, "TTL scan launch", hipGetLastError());
-  return ttl_replay(e, st);
-}
-
-extern "C" int cc_apply_batch(cc_engine* e, const cc_batch* c, uint64_t n, const cc_results* out, const cc_events* ev,
-                              void* stream) {
-  if (!e || !c || !out) return set_err(CC_ERR_INVALID, "null argument");
-  e->last_end = nullptr;  // (profiling markers: no begin marker is shared across calls)
-  if (n == 0) return CC_OK;
-  if (n > e->cfg.max_batch) return set_err(CC_ERR_CAPACITY, "batch larger than max_batch");
-  if (!c->inst || !c->op || !c->flags || !c->a || !c->b || !out->status || !out->value)
-    return set_err(CC_ERR_INVALID, "inst/op/flags/a/b columns and status/value outputs are required");
-  HIPCHECK(hipSetDevice(e->device));
-  hipStream_t st = stream ? (hipStream_t)stream : e->own_stream;
-  if (st != e->last_stream) HIPCHECK(hipStreamSynchronize(e->last_stream));
-  if (e->dev_dirty()) {  // registry writes queued by the control plane since the last device work
-    int rc = quiesce(e);
-    if (rc) return rc;
-  }
-  e->last_stream = st;
-  if ((((uintptr_t)out->status) & 3) || (((uintptr_t)out->value) & 15) || (((uintptr_t)c->inst) & 15))
-    return set_err(CC_ERR_INVALID, "inst and value must be 16-byte aligned, status 4-byte aligned");
-  if (e->map_bits && !c->key) return set_err(CC_ERR_INVALID, "an engine with maps needs the key column");
-  if (e->map_bits && !c->index)  // (log order of map events and the entries' claims: the tree-bin test, map_wide.hip)
-    return set_err(CC_ERR_INVALID, "an engine with maps needs the index column");
-  if (e->d_val_live && !c->index) return set_err(CC_ERR_INVALID, "CC_CFG_VALUE_RETAINED needs the index column");
-  if (ev && (!ev->pos || !ev->target || !ev->code || !ev->src || !ev->tag || !ev->payload || !ev->count))
-    return set_err(CC_ERR_INVALID, "event stream columns and count are required");
-  // Whole-map ops are barriers (map_wide.hip): find them (one sync), then apply the rows between them as segments.
-  e->bars.clear();
-  uint64_t clock_before = 0;  // the engine clock before this batch (TTL mode and barrier rows need it on the host)
-  e->szq_n = 0;
-  e->isc_rows.clear();
-  e->clr_n = 0;
-  e->clr_heavy.clear();
-  if (e->map_bits || e->coord_on) {
-    uint32_t nb = 0, ttl_seen = 0;
-    // Outside TTL mode the size / isEmpty, clear / removeValue and Delete rows of maps, sets and multimaps and a map's
-    // containsValue rows are answered in the stream (listed, their slots flagged); in TTL mode size / isEmpty rows are
-    // (the event replay answers them), the others are barriers.  A batch that turns TTL mode on (or lists more than a
-    // list holds) is scanned again with TTL mode's lists (or larger ones).
-    bool inline_size = e->map_bits && !e->ttl_live;
-    bool inline_ttl = e->map_bits && e->ttl_live;
-    for (int pass = 0;; ++pass) {
-      if ((inline_size || inline_ttl) && !e->d_szq) {
-        e->szq_cap = 1u << 20;
-        HIPCHECK(hipMalloc(&e->d_szq, sizeof(uint32_t) * e->szq_cap));
-        HIPCHECK(hipMalloc(&e->d_szq_n, sizeof(uint32_t)));
-      }
-      if (inline_size && !e->d_cvq) {  // containsValue candidates (map_cv.hip)
-        e->cvq_cap = 1u << 20;
-        HIPCHECK(hipMalloc(&e->d_cvq, sizeof(uint32_t) * e->cvq_cap));
-        HIPCHECK(hipMalloc(&e->d_isc, sizeof(uint32_t) * e->cvq_cap));
-        HIPCHECK(hipMalloc(&e->d_cvq_n, sizeof(uint32_t) * 2));
-        HIPCHECK(hipMalloc(&e->d_mfirst, sizeof(uint32_t) * e->cfg.max_resources));
-        HIPCHECK(hipMalloc(&e->d_maynull, e->cfg.max_resources));
-        e->clrq_cap = 1u << 20;  // clears in the stream (map_clear.hip)
-        HIPCHECK(hipMalloc(&e->d_clrq, sizeof(uint32_t) * e->clrq_cap));
-        HIPCHECK(hipMalloc(&e->d_clrq_n, sizeof(uint32_t)));
-        HIPCHECK(hipMalloc(&e->d_clr_keys, sizeof(uint64_t) * e->clrq_cap));
-        HIPCHECK(hipMalloc(&e->d_clr_keys2, sizeof(uint64_t) * e->clrq_cap));
-        HIPCHECK(hipMalloc(&e->d_clr_off, sizeof(uint32_t) * (e->cfg.max_resources + 1)));
-        HIPCHECK(hipMalloc(&e->d_clr_base, sizeof(uint32_t) * e->cfg.max_resources));
-        HIPCHECK(hipMalloc(&e->d_clr_eend, e->cfg.max_resources));
-        e->clr_temp_bytes = std::max<size_t>(clr_sort_temp_bytes(e->clrq_cap), 256);
-        HIPCHECK(hipMalloc(&e->d_clr_temp, e->clr_temp_bytes));
-      }
-      if (e->szq_flagged) {
-        if (launch_mflag_clear(e->d_msmall, e->cfg.max_resources, st)) return set_err(CC_ERR_HIP, "map flags", hipGetLastError());
-        e->szq_flagged = false;
-      }
-      HIPCHECK(hipMemsetAsync(e->d_ttl_seen, 0, sizeof(uint32_t), st));
-      if (launch_map_barriers(c->inst, c->op, c->aux, n, e->d_inst_res, e->d_res_type, e->cfg.max_instances, e->d_bar,
-                              e->d_bar_n, kBarCap, e->d_ttl_seen, inline_size || inline_ttl ? e->d_szq : nullptr,
-                              inline_size || inline_ttl ? e->d_szq_n : nullptr, e->szq_cap, e->d_msmall,
-                              inline_size ? e->d_cvq : nullptr, inline_size ? e->d_cvq_n : nullptr, e->cvq_cap,
-                              inline_size ? e->d_mfirst : nullptr, e->cfg.max_resources,
-                              inline_size ? e->d_clrq : nullptr, inline_size ? e->d_clrq_n : nullptr, e->clrq_cap, st))
-        return set_err(CC_ERR_HIP, "map barrier scan launch", hipGetLastError());
-      if (inline_size) {  // containsValue candidates: in the stream, or barriers (map_cv.hip)
-        CvBatchArgs cb{};
-        cb.inst = c->inst;
-        cb.op = c->op;
-        cb.flags = c->flags;
-        cb.n = n;
-        cb.inst_res = e->d_inst_res;
-        cb.max_inst = e->cfg.max_instances;
-        cb.mflag = e->d_msmall;
-        cb.tbl_word = e->d_tbl_word;
-        cb.entries = e->map_entries;
-        cb.cvq = e->d_cvq;
-        cb.cvq_n = e->d_cvq_n;
-        cb.cvq_cap = e->cvq_cap;
-        cb.mfirst = e->d_mfirst;
-        cb.maynull = e->d_maynull;
-        cb.R = e->cfg.max_resources;
-        cb.bar = e->d_bar;
-        cb.bar_n = e->d_bar_n;
-        cb.bar_cap = kBarCap;
-        cb.isc = e->d_isc;
-        cb.isc_n = e->d_cvq_n + 1;
-        if (launch_cv_batch(cb, st)) return set_err(CC_ERR_HIP, "containsValue classify launch", hipGetLastError());
-      }
-      uint32_t qn = 0, cvn[2] = {0, 0}, cln = 0;
-      {  // (one round trip: every counter into the pinned words, then one synchronize)
-        uint64_t* const pin = e->h_pin;
-        uint32_t* const p32 = reinterpret_cast<uint32_t*>(pin + 1);
-        HIPCHECK(hipMemcpyAsync(pin, e->d_clock, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipMemcpyAsync(p32 + 0, e->d_bar_n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipMemcpyAsync(p32 + 1, e->d_ttl_seen, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        if (inline_size || inline_ttl) HIPCHECK(hipMemcpyAsync(p32 + 2, e->d_szq_n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        if (inline_size) HIPCHECK(hipMemcpyAsync(p32 + 3, e->d_cvq_n, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        if (inline_size) HIPCHECK(hipMemcpyAsync(p32 + 5, e->d_clrq_n, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        if (e->map_bits) {  // the batch's first and last log index (map event positions, below)
-          HIPCHECK(hipMemcpyAsync(pin + 4, c->index, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-          HIPCHECK(hipMemcpyAsync(pin + 5, c->index + n - 1, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        }
-        HIPCHECK(hipStreamSynchronize(st));
-        // Map events are keyed by their position (log index - the sub-batch's first, 32 bits: common.h kEvPosBits).
-        // A batch whose whole index range fits needs no cut; else each sub-batch ends before its first row 2^32 past
-        // its start (k_span_cut, one round trip per sub-batch, only then)
-        if (e->map_bits) e->span_cut = n && pin[5] - pin[4] >= (1ull << kEvPosBits);
-        clock_before = pin[0];
-        nb = p32[0];
-        ttl_seen = p32[1];
-        if (inline_size || inline_ttl) qn = p32[2];
-        if (inline_size) cvn[0] = p32[3], cvn[1] = p32[4], cln = p32[5];
-      }
-      if (!inline_size && !inline_ttl) break;
-      e->szq_flagged = qn > 0 || cvn[0] > 0 || cln > 0;
-      if (inline_size && (ttl_seen || pass > 2)) {  // this batch turns TTL mode on: containsValue and clear become
-        inline_size = false;                        // barriers again, size / isEmpty stay in the stream
-        inline_ttl = pass <= 2;
-        continue;
-      }
-      if (qn > e->szq_cap) {  // a larger list, then the same scan again
-        HIPCHECK(hipFree(e->d_szq));
-        e->d_szq = nullptr;
-        e->szq_cap = qn;
-        HIPCHECK(hipMalloc(&e->d_szq, sizeof(uint32_t) * e->szq_cap));
-        continue;
-      }
-      if (cln > e->clrq_cap) {
-        HIPCHECK(hipFree(e->d_clrq));
-        HIPCHECK(hipFree(e->d_clr_keys));
-        HIPCHECK(hipFree(e->d_clr_keys2));
-        HIPCHECK(hipFree(e->d_clr_temp));
-        e->clrq_cap = cln;
-        HIPCHECK(hipMalloc(&e->d_clrq, sizeof(uint32_t) * e->clrq_cap));
-        HIPCHECK(hipMalloc(&e->d_clr_keys, sizeof(uint64_t) * e->clrq_cap));
-        HIPCHECK(hipMalloc(&e->d_clr_keys2, sizeof(uint64_t) * e->clrq_cap));
-        e->clr_temp_bytes = std::max<size_t>(clr_sort_temp_bytes(e->clrq_cap), 256);
-        HIPCHECK(hipMalloc(&e->d_clr_temp, e->clr_temp_bytes));
-        continue;
-      }
-      if (cvn[0] > e->cvq_cap) {
-        HIPCHECK(hipFree(e->d_cvq));
-        HIPCHECK(hipFree(e->d_isc));
-        e->cvq_cap = cvn[0];
-        HIPCHECK(hipMalloc(&e->d_cvq, sizeof(uint32_t) * e->cvq_cap));
-        HIPCHECK(hipMalloc(&e->d_isc, sizeof(uint32_t) * e->cvq_cap));
-        continue;
-      }
-      e->szq_n = qn;
-      if (inline_ttl) break;  // (TTL mode lists size / isEmpty rows only)
-      int rc = cv_rows(e, cvn[1], st);  // the in-stream rows, sorted, on the host too
-      if (rc) return rc;
-      if ((rc = clr_rows(e, cln, c, st))) return rc;  // the in-stream clears: sorted by (map, row), offsets
-      break;
-    }
-    if (ttl_seen && !e->ttl_live) {  // TTL mode for good: sizes and capacities from commit + expiry events
-      e->ttl_live = true;
-      e->small_live = false;  // (every map's events are replayed in TTL mode, the small ones' key sets included)
-    }
-    // The leak log (commits dropped without clean()) is drained before every batch of an engine that can add to it:
-    // every multimap put, and with value events every re-listen (AtomicValueState.listen :41-49) may land there, at
-    // most one entry per row, so the drained log gets room for n more; a coordination engine without value events
-    // adds entries only in the close fan-out (cc_sessions_close sizes the log for that itself) but is drained here
-    // too, so nothing accumulates across batches toward the log's end.
-    if (e->has_mmaps || e->coord_on) {
-      int rc = drain_leaks(e);
-      const bool may_leak = e->has_mmaps || (e->cfg.flags & CC_CFG_VALUE_EVENTS);
-      if (!rc && may_leak) rc = ensure_leak(e, n);
-      if (rc) return rc;
-    }
-    if (nb > kBarCap) {
-      // More barrier rows than one listing holds: the batch runs as two consecutive batches (a batch boundary is a
-      // point of the log like any other: timers due by its clock have fired there in both timer orders, A8).  With an
-      // event stream the second half's events are appended after the first's, their rows moved by h.
-      if (n < 2)
-        return set_err(CC_ERR_CAPACITY, "more whole-map ops and group schedules in one row than kBarCap");
-      const uint64_t h = n / 2;
-      auto shift = [h](const auto* p) { return p ? p + h : p; };
-      const cc_batch c2{shift(c->index), shift(c->time), shift(c->inst), shift(c->op), shift(c->flags), shift(c->key),
-                        shift(c->a), shift(c->b), shift(c->aux)};
-      const cc_results o2{out->status + h, out->value + h};
-      int rc = cc_apply_batch(e, c, h, out, ev, stream);
-      if (rc || !ev || !e->coord_on) return rc ? rc : cc_apply_batch(e, &c2, n - h, &o2, ev, stream);
-      uint64_t n1 = 0, n2 = 0;
-      HIPCHECK(hipMemcpyAsync(&n1, ev->count, sizeof n1, hipMemcpyDeviceToHost, st));
-      HIPCHECK(hipStreamSynchronize(st));
-      if (n1 > ev->capacity) return set_err(CC_ERR_CAPACITY, "event stream capacity exceeded");
-      if (!e->d_half_count) HIPCHECK(hipMalloc(&e->d_half_count, sizeof(uint64_t)));
-      cc_events ev2 = *ev;
-      ev2.pos += n1, ev2.target += n1, ev2.code += n1, ev2.src += n1, ev2.tag += n1, ev2.payload += n1;
-      ev2.capacity -= n1;
-      ev2.count = e->d_half_count;
-      if ((rc = cc_apply_batch(e, &c2, n - h, &o2, &ev2, stream))) return rc;
-      HIPCHECK(hipMemcpyAsync(&n2, e->d_half_count, sizeof n2, hipMemcpyDeviceToHost, st));
-      HIPCHECK(hipStreamSynchronize(st));
-      if (launch_ev_shift(ev2.pos, std::min(n2, ev2.capacity), (uint32_t)h, st))
-        return set_err(CC_ERR_HIP, "event row shift launch", hipGetLastError());
-      const uint64_t total = n1 + n2;
-      HIPCHECK(hipMemcpyAsync(ev->count, &total, sizeof total, hipMemcpyHostToDevice, st));
-      HIPCHECK(hipStreamSynchronize(st));  // (total is a host local)
-      return CC_OK;
-    }
-    if (nb) {  // the barrier rows in log order, then their columns in one gather (one copy back, not one per field)
-      e->bars.resize(nb);
-      HIPCHECK(hipMemcpy(e->bars.data(), e->d_bar, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
-      std::sort(e->bars.begin(), e->bars.end());
-      if (nb > e->bar_rows_cap) {
-        if (e->d_bar_rows) HIPCHECK(hipFree(e->d_bar_rows));
-        e->d_bar_rows = nullptr;
-        e->bar_rows_cap = 0;
-        HIPCHECK(hipMalloc(&e->d_bar_rows, sizeof(BarRow) * nb));
-        e->bar_rows_cap = nb;
-      }
-      HIPCHECK(hipMemcpyAsync(e->d_bar, e->bars.data(), sizeof(uint32_t) * nb, hipMemcpyHostToDevice, st));
-      if (launch_bar_fields(e->d_bar, nb, c->inst, c->op, c->flags, c->a, c->key, c->aux, c->index, c->time,
-                            e->d_bar_rows, st))
-        return set_err(CC_ERR_HIP, "barrier rows gather launch", hipGetLastError());
-      e->bar_rows.resize(nb);
-      HIPCHECK(hipMemcpyAsync(e->bar_rows.data(), e->d_bar_rows, sizeof(BarRow) * nb, hipMemcpyDeviceToHost, st));
-      HIPCHECK(hipStreamSynchronize(st));
-    }
-  }
-  if (e->coord_on || e->ttl_live) {  // events of this batch start at 0; the log clock must not go backwards inside it
-    if (e->coord_on) HIPCHECK(hipMemsetAsync(e->d_ev_total, 0, sizeof(unsigned long long), st));
-    // (without barrier rows every row goes through k_part_ext, which checks it against the row before it)
-    if (!e->bars.empty() && launch_time_check(c->time, n, e->d_clock, e->d_err, st))
-      return set_err(CC_ERR_HIP, "time check", hipGetLastError());
-  }
-  // Group timers: where each pending one fires in this batch, and where the timer of each schedule row of the batch
-  // would (the clock at row r is max(clock_before, time[r])): the first row r >= from whose clock reaches the deadline
-  // -> the boundary the timer fires at (manager mode: after row r; module mode: before it, A8), or ~0 when no row of
-  // this batch reaches it.  One device search for all of them (k_fire_bounds).
-  const bool deferred = (e->cfg.flags & CC_CFG_TIMERS_DEFERRED) != 0;
-  auto clock_at = [&](const BarRow& br) { return c->time ? std::max(br.t_row, clock_before) : clock_before; };
-  std::vector<uint64_t> sched_dl(e->bars.size(), 0), sched_fb(e->bars.size(), ~0ull);  // per barrier (schedule rows)
-  {
-    std::vector<uint64_t> dl, from;
-    std::vector<uint32_t> who;  // < gtimers.size(): a pending timer; else gtimers.size() + barrier index
-    for (size_t q = 0; q < e->gtimers.size(); ++q) {
-      dl.push_back(e->gtimers[q].deadline);
-      from.push_back(0);
-      who.push_back((uint32_t)q);
-    }
-    for (size_t k = 0; k < e->bars.size(); ++k) {
-      const BarRow& br = e->bar_rows[k];
-      if (br.op != CC_OP_GROUP_SCHEDULE) continue;
-      const uint64_t delay = c->aux ? br.aux : 0;
-      sched_dl[k] = clock_at(br) + ((int64_t)delay > 0 ? delay : 0);  // schedule :86-103
-      dl.push_back(sched_dl[k]);
-      from.push_back(deferred ? e->bars[k] : (uint64_t)e->bars[k] + 1);
-      who.push_back((uint32_t)(e->gtimers.size() + k));
-    }
-    const uint32_t m = (uint32_t)dl.size();
-    if (m) {
-      if (m > e->fb_cap) {
-        if (e->d_fb) HIPCHECK(hipFree(e->d_fb));
-        e->d_fb = nullptr;
-        e->fb_cap = 0;
-        HIPCHECK(hipMalloc(&e->d_fb, sizeof(uint64_t) * 3 * m));
-        e->fb_cap = m;
-      }
-      std::vector<uint64_t> res(m);
-      HIPCHECK(hipMemcpyAsync(e->d_fb, dl.data(), 8ull * m, hipMemcpyHostToDevice, st));
-      HIPCHECK(hipMemcpyAsync(e->d_fb + m, from.data(), 8ull * m, hipMemcpyHostToDevice, st));
-      if (launch_fire_bounds(c->time, n, clock_before, e->d_fb, e->d_fb + m, m, deferred, e->d_fb + 2 * m, st))
-        return set_err(CC_ERR_HIP, "timer bounds launch", hipGetLastError());
-      HIPCHECK(hipMemcpyAsync(res.data(), e->d_fb + 2 * m, 8ull * m, hipMemcpyDeviceToHost, st));
-      HIPCHECK(hipStreamSynchronize(st));
-      for (uint32_t i = 0; i < m; ++i) {
-        if (who[i] < e->gtimers.size()) e->gtimers[who[i]].fire_b = res[i];
-        else sched_fb[who[i] - e->gtimers.size()] = res[i];
-      }
-    }
-  }
-  if (e->map_bits && !e->ttl_live) {  // the batch's hot map keys (apply_map_hot.hip): counted once, bound per sub-batch
-    HotArgs hb{};
-    hb.inst = c->inst;
-    hb.flags = c->flags;
-    hb.key = c->key;
-    hb.lo = 0;
-    hb.hi = n;
-    hb.inst_res = e->d_inst_res;
-    hb.res_type = e->d_res_type;
-    hb.max_inst = e->cfg.max_instances;
-    hb.hot_samp = e->d_hot_samp;
-    hb.hot_cand = e->d_hot_cand;
-    hb.hot_cand_n = e->d_hot_cand_n;
-    if (launch_map_hot_detect(hb, st)) return set_err(CC_ERR_HIP, "hot-key detect launch", hipGetLastError());
-  }
-  uint64_t cur = 0;
-  size_t bi = 0;
-  uint64_t own_lo = 0;  // TTL mode: the first timer-firing boundary no sub-batch has owned yet (common.h TtlEmit)
-  for (;;) {
-  // the next thing in log order: a barrier row, or a group timer firing (timers first at the same boundary)
-  const uint64_t bar_b = bi < e->bars.size() ? (uint64_t)e->bars[bi] : ~0ull;
-  size_t tk = e->gtimers.size();
-  for (size_t q = 0; q < e->gtimers.size(); ++q) {
-    const auto& g = e->gtimers[q];
-    if (g.fire_b == ~0ull || g.fire_b < cur) continue;
-    if (tk == e->gtimers.size()) { tk = q; continue; }
-    const auto& b = e->gtimers[tk];
-    if (std::make_tuple(g.fire_b, g.deadline, g.id) < std::make_tuple(b.fire_b, b.deadline, b.id)) tk = q;
-  }
-  const uint64_t tim_b = tk < e->gtimers.size() ? e->gtimers[tk].fire_b : ~0ull;
-  const int action = (tim_b != ~0ull && tim_b <= bar_b) ? 2 : (bar_b != ~0ull ? 1 : 0);
-  const uint64_t seg_lo = cur;
-  const uint64_t seg_hi = action == 2 ? tim_b : (action == 1 ? bar_b : n);
-  for (uint64_t lo = seg_lo, hi; lo < seg_hi; lo = hi) {
-    hi = std::min(seg_hi, lo + (e->ext ? e->sub_ext : e->sub_batch));
-    if (e->sm_alt_on && !e->ttl_live) {  // the other event-buffer set, once its replay is done (engine_state.h SmSet)
-      std::swap(e->d_sm_key, e->sm_alt.key);
-      std::swap(e->d_sm_key2, e->sm_alt.key2);
-      std::swap(e->d_sm_val, e->sm_alt.val);
-      std::swap(e->d_sm_val2, e->sm_alt.val2);
-      std::swap(e->d_sm_pay, e->sm_alt.pay);
-      std::swap(e->d_sm_cseg, e->sm_alt.cseg);
-      e->sm_cur ^= 1;
-      int rc = wait_replay(e, e->sm_cur, st);  // (its replay's exit marks fold into the snapshot here)
-      if (rc) return rc;
-    }
-    for (const auto& hv : e->clr_heavy) {  // at most 127 in-stream clears of one map per sub-batch (map_clear.hip)
-      const size_t q = (size_t)(std::lower_bound(hv.begin(), hv.end(), (uint32_t)lo) - hv.begin());
-      if (q + 127 < hv.size() && hv[q + 127] < hi) hi = hv[q + 127];
-    }
-    // this sub-batch's in-stream containsValue rows (at most kCvMaxRows: a denser run ends the sub-batch earlier)
-    size_t cv_b = 0, cv_e = 0;
-    if (!e->isc_rows.empty()) {
-      cv_b = (size_t)(std::lower_bound(e->isc_rows.begin(), e->isc_rows.end(), (uint32_t)lo) - e->isc_rows.begin());
-      cv_e = (size_t)(std::lower_bound(e->isc_rows.begin(), e->isc_rows.end(), (uint32_t)hi) - e->isc_rows.begin());
-      if (cv_e - cv_b > kCvMaxRows) {
-        cv_e = cv_b + kCvMaxRows;
-        hi = e->isc_rows[cv_e];
-      }
-    }
-    if (e->span_cut && !e->ttl_live) {  // (TTL mode positions events by row, 2 (row - lo) + 1: always within 32 bits)
-      HIPCHECK(hipMemsetAsync(e->d_span_cut, 0xFF, sizeof(uint64_t), st));
-      if (launch_span_cut(c->index, lo, hi, e->d_span_cut, st)) return set_err(CC_ERR_HIP, "span cut launch", hipGetLastError());
-      HIPCHECK(hipMemcpyAsync(e->h_pin + 6, e->d_span_cut, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-      HIPCHECK(hipStreamSynchronize(st));
-      if (e->h_pin[6] > lo && e->h_pin[6] < hi) hi = e->h_pin[6];
-      if (!e->isc_rows.empty())  // (the in-stream containsValue rows of the shortened sub-batch)
-        cv_e = (size_t)(std::lower_bound(e->isc_rows.begin(), e->isc_rows.end(), (uint32_t)hi) - e->isc_rows.begin());
-    }
-    const uint32_t cv_n = (uint32_t)(cv_e - cv_b);
-    const bool clr_on = e->clr_n > 0;  // clears in the stream in this batch (map_clear.hip)
-    ClrSubArgs ca{};
-    ClrCtx cctx{};
-    if (clr_on) {
-      int rc = ensure_small(e);  // (the cleared maps' sizes ride the map event buffer)
-      if (rc) return rc;
-      ca.keys = e->d_clr_keys2;
-      ca.n = e->clr_n;
-      ca.off = e->d_clr_off;
-      ca.R = e->cfg.max_resources;
-      ca.lo = lo;
-      ca.hi = hi;
-      ca.base = e->d_clr_base;
-      ca.eend = e->d_clr_eend;
-      ca.mflag = e->d_msmall;
-      ca.err = e->d_err;
-      ca.index = c->index;
-      ca.ev_key = e->d_sm_key;
-      ca.ev_val = e->d_sm_val;
-      ca.ev_pay = e->d_sm_pay;
-      ca.ev_cap = (uint32_t)e->sm_cap;
-      ca.ev_ctl = e->d_sm_ctl;
-      ca.cgen = e->d_mw_cgen;
-      {  // the epoch buckets: at most 1024 per map and ~64 MB in all
-        uint32_t nbmax = 16;
-        while (nbmax < 1024 && (uint64_t)(2 * nbmax) * e->cfg.max_resources <= (64ull << 20)) nbmax <<= 1;
-        uint32_t sh = 0;
-        while (((hi - lo + (1ull << sh) - 1) >> sh) > nbmax) ++sh;
-        ca.bshift = sh;
-        ca.nb = (uint32_t)((hi - lo + (1ull << sh) - 1) >> sh);
-        const size_t need = (size_t)nbmax * e->cfg.max_resources;
-        if (e->clr_btab_bytes < need) {
-          if (e->d_clr_btab) (void)hipFree(e->d_clr_btab);
-          e->d_clr_btab = nullptr;
-          HIPCHECK(hipMalloc(&e->d_clr_btab, need));
-          e->clr_btab_bytes = need;
-        }
-        ca.btab = e->d_clr_btab;
-      }
-      if (launch_clr_sub(ca, st)) return set_err(CC_ERR_HIP, "clear epochs launch", hipGetLastError());
-      cctx = ClrCtx{e->d_msmall, e->d_clr_keys2, e->d_clr_off, e->d_clr_base, e->d_clr_eend, lo, e->d_tbl_ep,
-                    e->d_clr_btab, ca.nb, ca.bshift};
-    }
-    CvSubArgs cva{};
-    cva.clr = cctx;
-    ++e->stat_subbatches;
-    e->stat_isc += cv_n;
-    const uint32_t tiles = (uint32_t)((hi - lo + kTile - 1) / kTile);
-    SizeArgs sz{};       // this sub-batch's size / isEmpty rows (map_small.hip)
-    bool sized = false;  // the event pipeline ran (its counters are reset after the answers)
-    bool ttl_pending = false;  // TTL mode: the sub-batch's event replay, after the unpermute
-    uint32_t cv_E = 0;         // in-stream containsValue events (final once the map apply kernels ran)
-    bool cv_known = false;     // (read with the map events' count: one host round trip per sub-batch, not two)
-    uint32_t sized_events = 0;
-    if (e->map_bits && e->ttl_live) {  // TTL mode: every key goes through its region (timers are walked in order)
-      HIPCHECK(hipMemsetAsync(e->d_hot_n, 0, sizeof(uint32_t), st));
-    }
-    HotArgs ha{};
-    if (e->map_bits && !e->ttl_live) {  // hot map keys of this sub-batch (routed to their own buckets by the partition)
-      ha.inst = c->inst;
-      ha.flags = c->flags;
-      ha.key = c->key;
-      ha.lo = lo;
-      ha.hi = hi;
-      ha.inst_res = e->d_inst_res;
-      ha.res_type = e->d_res_type;
-      ha.max_inst = e->cfg.max_instances;
-      ha.mrec = e->d_mrec;
-      ha.cb = c->b;
-      ha.ttab = e->d_ttab;
-      ha.tiles = tiles;
-      ha.sb = e->sb_total();
-      ha.sb_val = e->sb;
-      ha.map_bits = e->map_bits;
-      ha.tbl_key = e->d_tbl_key;
-      ha.tbl_word = e->d_tbl_word;
-      ha.tbl_val = e->d_tbl_val;
-      ha.tbl_ci = e->d_tbl_ci;
-      ha.tbl_ins = e->d_tbl_ins;
-      ha.tbl_claim = e->d_tbl_claim;
-      ha.idx0 = c->index ? c->index + lo : nullptr;
-      ha.hot = e->d_hot;
-      ha.hot_n = e->d_hot_n;
-      ha.hot_rpre = e->d_hot_rpre;
-      ha.hot_rstart = e->d_hot_rstart;
-      ha.hot_len = e->d_hot_len;
-      ha.hot_cond = e->d_hot_cond;
-      ha.hot_agg = e->d_hot_agg;
-      ha.hot_s0 = e->d_hot_s0;
-      ha.hot_samp = e->d_hot_samp;
-      ha.hot_cand = e->d_hot_cand;
-      ha.hot_cand_n = e->d_hot_cand_n;
-      ha.hot_meta = e->d_hot_meta;
-      ha.rst_status = e->d_rst_status;
-      ha.rst_value = e->d_rst_value;
-      ha.hot_msz = e->d_hot_msz;
-      ha.msmall = nullptr;  // (every map's keys are hot-routed)
-      if (e->small_live || e->szq_n || clr_on) {  // small / size-queried / cleared maps' hot commits: map events
-        int rc = ensure_small(e);
-        if (rc) return rc;
-        if (!c->index) return set_err(CC_ERR_INVALID, "an engine with maps needs the index column (log order)");
-        ha.hc.clr = cctx;  // (cleared maps: commit epochs, map_clear.hip)
-        ha.hc.mflag = e->d_msmall;
-        ha.hc.hh_key = e->d_hh_key;
-        ha.hc.hh_val = e->d_hh_val;
-        ha.hc.hh_n = e->hh_n;
-        ha.hc.xr = e->d_mrec;
-        ha.hc.lo = lo;
-        ha.hc.ev_key = e->d_sm_key;
-        ha.hc.ev_val = e->d_sm_val;
-        ha.hc.ev_pay = e->d_sm_pay;
-        ha.hc.ev_cap = (uint32_t)e->sm_cap;
-        ha.hc.ev_ctl = e->d_sm_ctl;
-        ha.hc.idx0p = c->index + lo;
-        ha.hc.tbl_ep = e->d_tbl_ep;
-      }
-      ha.err = e->d_err;
-      ha.mark = marker_of(e);
-      static const bool no_hot = diag_env("CC_NO_HOT");  // diagnostics: every key through its region
-      if (no_hot) HIPCHECK(hipMemsetAsync(e->d_hot_n, 0, sizeof(uint32_t), st));
-      else if (launch_map_hot_bind(ha, st)) return set_err(CC_ERR_HIP, "hot-key bind launch", hipGetLastError()); DBG_SYNC("hot-key bind launch");
-    }
-    PartArgs pa{};
-    pa.inst = c->inst;
-    pa.op = c->op;
-    pa.flags = c->flags;
-    pa.a = c->a;
-    pa.b = c->b;
-    pa.key = c->key;
-    pa.index = c->index;
-    pa.aux = (e->coord_on || e->ttl_live) ? c->aux : nullptr;  // maps read ttl only in TTL mode (the scan saw none)
-    pa.time = c->time;
-    pa.clock_base = e->d_clock;
-    pa.ext_flags = ((e->cfg.flags & CC_CFG_VALUE_EVENTS) ? kExtValue : 0u) | ((e->cfg.flags & CC_CFG_TIMERS_DEFERRED) ? kExtDeferred : 0u) |
-                   ((e->coord_on || e->ttl_live) && e->bars.empty() ? kExtTimeCheck : 0u);
-    pa.err = e->d_err;
-    pa.ext = e->ext;
-    pa.lo = lo;
-    pa.hi = hi;
-    pa.inst_res = e->d_inst_res;
-    pa.inst_id = e->coord_on ? e->d_inst_id : nullptr;
-    pa.res_type = e->d_res_type;
-    pa.sb_kind = e->d_sb_kind;
-    pa.max_inst = e->cfg.max_instances;
-    pa.sb = e->sb_total();
-    pa.sb_val = e->sb;
-    pa.sbq_base = e->quarter ? e->sbq_base() : 0u;
-    pa.map_bits = e->map_bits;
-    pa.hot = e->d_hot;
-    pa.hot_n = e->d_hot_n;
-    pa.st_meta = e->d_st_meta;
-    pa.st_ab = e->d_st_ab;
-    pa.xrec = e->d_xrec;
-    pa.mrec = e->d_mrec;
-    pa.hot_meta = e->d_hot_meta;
-    pa.clr = cctx;  // (each map commit's clear epoch into its meta word)
-    pa.cpos = e->d_cpos;
-    pa.ttab = e->d_ttab;
-    pa.dummy = e->sub_batch;
-    const bool v3 = !e->ext;  // value-only engines: value_path.hip
-    pa.v3 = v3;
-    // the sub-batch's results back to log order (every staged result is written by then); launched early, beside
-    // the host's counter readback, when nothing after that point writes staged results (below)
-    bool unpermuted = false;
-    auto unpermute = [&]() -> int {
-      UnpermuteArgs ua{};
-      ua.cpos = e->d_cpos;
-      ua.ttab = e->d_ttab;
-      ua.sb = e->sb_total();
-      ua.lo = lo;
-      ua.hi = hi;
-      ua.rst_status = e->d_rst_status;
-      ua.rst_value = e->d_rst_value;
-      ua.out_status = out->status;
-      ua.out_value = out->value;
-      ua.dummy_status = e->d_rst_status + e->sub_batch;
-      ua.dummy_value = e->d_rst_value + e->sub_batch;
-      ua.v3 = v3;
-      ua.words = reinterpret_cast<const uint64_t*>(e->d_st_ab);
-      ua.mark = marker_of(e);
-      if (launch_unpermute(ua, st)) return set_err(CC_ERR_HIP, "unpermute launch", hipGetLastError());
-      unpermuted = true;
-      return CC_OK;
-    };
-
-    pa.mark = marker_of(e);
-    if (launch_partition(pa, st)) {
-      const hipError_t x = hipGetLastError();
-      if (x == hipSuccess) return set_err(CC_ERR_CAPACITY, "the partition's LDS cannot hold this engine's buckets");
-      return set_err(CC_ERR_HIP, "partition launch", x);
-    }
-    DBG_SYNC("partition launch");
-    {
-      int rc = launch_pending_replay(e, st);  // (the previous sub-batch's small-map replay, beside this one's work)
-      if (rc) return rc;
-    }
-    if (e->map_bits && e->ttl_live && launch_map_rows(e->d_cpos, lo, hi, e->d_map_row, st))
-      return set_err(CC_ERR_HIP, "map rows launch", hipGetLastError());
-    ValueArgs va{};
-    va.st_meta = e->d_st_meta;
-    va.st_ab = e->d_st_ab;
-    va.ttab = e->d_ttab;
-    va.tiles = v3 ? (uint32_t)((hi - lo + kV3Tile - 1) / kV3Tile) : tiles;
-    va.v3 = v3;
-
-    va.ca = c->a;
-    va.cb = c->b;
-    va.lo = lo;
-    va.sb = e->sb_total();
-    va.sb_val = e->sb;
-    va.sb_kind = e->d_sb_kind;
-    va.val_meta = e->d_val_meta;
-    va.val_v = e->d_val_v;
-    va.rst_status = e->d_rst_status;
-    va.rst_value = e->d_rst_value;
-    va.dummy = e->sub_batch;
-    va.err = e->d_err;
-    va.mark = marker_of(e);
-    if ((e->has_values || !e->ext) && launch_apply_value(va, st)) return set_err(CC_ERR_HIP, "apply launch", hipGetLastError()); DBG_SYNC("apply launch");
-    if (cv_n) {  // in-stream containsValue: operand set, initial counts, query events (map_cv.hip)
-      int rc = ensure_cv(e);
-      if (rc) return rc;
-      uint32_t sc = 1024;
-      while (sc < 2 * cv_n) sc <<= 1;
-      cva.cv.mflag = e->d_msmall;
-      cva.cv.set = e->d_cvset;
-      cva.cv.mask = sc - 1;
-      cva.cv.bloom = e->d_cvbloom;
-      cva.cv.bbits = 16;
-      while (cva.cv.bbits < kCvBloomMaxBits && (1ull << cva.cv.bbits) < 16ull * cv_n) ++cva.cv.bbits;
-      cva.cv.ev_key = e->d_cvev_key;
-      cva.cv.ev_val = e->d_cvev_val;
-      cva.cv.cap = e->cvev_cap;
-      cva.cv.ctl = e->d_cvev_ctl;
-      cva.cv.idx0p = c->index + lo;
-      cva.set = e->d_cvset;
-      cva.cnt = e->d_cvcnt;
-      cva.isc = e->d_isc2 + cv_b;
-      cva.isc_n = cv_n;
-      cva.lo = lo;
-      cva.inst = c->inst;
-      cva.flags = c->flags;
-      cva.a = c->a;
-      cva.index = c->index;
-      cva.inst_res = e->d_inst_res;
-      cva.tbl_word = e->d_tbl_word;
-      cva.tbl_val = e->d_tbl_val;
-      cva.entries = e->map_entries;
-      cva.err = e->d_err;
-      cva.key2 = e->d_cvev_key2;
-      cva.val2 = e->d_cvev_val2;
-      cva.seg = e->d_cvseg;
-      cva.nseg = e->d_cvseg + e->cvset_cap;
-      cva.coll = e->d_cvseg;          // (free until the answers' runs: the prepare's collision list)
-      cva.coll_n = e->d_cvev_ctl + 1;
-      cva.temp = e->d_cvtemp;
-      cva.temp_bytes = e->cvtemp_bytes;
-      cva.out_status = out->status;
-      cva.out_value = out->value;
-      if (launch_cv_prepare(cva, st)) return set_err(CC_ERR_HIP, "containsValue prepare launch", hipGetLastError());
-      ha.cv = cva.cv;
-    }
-    if (e->map_bits) {
-      if (!e->ttl_live && launch_map_hot_apply(ha, st)) return set_err(CC_ERR_HIP, "hot-key apply launch", hipGetLastError());
-      MapArgs ma{};
-      ma.cv = cva.cv;
-      ma.clr = cctx;
-      ma.mrec = e->d_mrec;
-      ma.cb = c->b;
-      ma.lo = lo;
-      ma.ttab = e->d_ttab;
-      ma.tiles = tiles;
-      ma.sb = e->sb_total();
-      ma.sb_val = e->sb;
-      ma.map_bits = e->map_bits;
-      ma.tbl_key = e->d_tbl_key;
-      ma.tbl_word = e->d_tbl_word;
-      ma.tbl_val = e->d_tbl_val;
-      ma.tbl_ci = e->d_tbl_ci;
-      ma.tbl_ins = e->d_tbl_ins;
-      ma.tbl_claim = e->d_tbl_claim;
-      ma.idx0 = c->index ? c->index + lo : nullptr;
-      ma.dropped = e->d_mw_drop;
-      ma.cgen = e->d_mw_cgen;
-      ma.cset = e->d_cset;
-      ma.cset_mask = e->cset_mask;
-      ma.cset_full = e->d_cset_full;
-      ma.ttl = e->ttl_live;
-      ma.tbl_dl = e->d_tbl_dl;
-      ma.map_row = e->d_map_row;
-      ma.time = c->time;
-      ma.aux = c->aux;
-      ma.clock_base = e->d_clock;
-      ma.deferred = (e->cfg.flags & CC_CFG_TIMERS_DEFERRED) != 0;
-      ma.rst_status = e->d_rst_status;
-      ma.rst_value = e->d_rst_value;
-      ma.rst_msz = e->d_rst_msz;
-      ma.err = e->d_err;
-      ma.mark = marker_of(e);
-      TtlEmit te{};
-      if (e->ttl_live) {  // this sub-batch owns the timer-firing boundaries [own_lo, hi] (common.h TtlEmit)
-        int rc = ensure_small(e);
-        if (rc) return rc;
-        te = ttl_emit_args(e, c->time, n, lo, own_lo, hi, 0);
-        ma.ttl_emit = te;
-      }
-      if (launch_apply_map(ma, st)) return set_err(CC_ERR_HIP, "map apply launch", hipGetLastError()); DBG_SYNC("map apply launch");
-      if (clr_on && launch_clr_gen(ca, st)) return set_err(CC_ERR_HIP, "clear generation launch", hipGetLastError());
-      if (e->ttl_live) {  // exact sizes and capacities in TTL mode: the sub-batch's commits and expiries as events
-        if (launch_ttl_scan(te, e->d_clock, e->d_tbl_word, e->d_tbl_key, e->d_tbl_dl, e->map_entries, e->d_err, st))
-          return set_err(CC_ERR_HIP, "TTL scan launch", hipGetLastError());
-        MapSizeArgs za{};
-        za.ttab = e->d_ttab;
-        za.cpos = e->d_cpos;
-        za.tiles = tiles;
-        za.rows = hi - lo;
-        za.sb = e->sb_total();
-        za.k0 = e->sb;
-        za.k1 = e->sbq_base();
-        za.sb_hot = e->sb + (1u << e->map_bits);
-        za.rst_msz = e->d_rst_msz;
-        za.hot = e->d_hot;
-        za.hot_n = e->d_hot_n;  // (0: no hot keys in TTL mode)
-        za.hot_len = e->d_hot_len;
-        za.hot_rpre = e->d_hot_rpre;
-        za.hot_msz = e->d_hot_msz;
-        za.res_type = e->d_res_type;
-        za.max_resources = e->cfg.max_resources;
-        za.tcnt = e->d_msz_tcnt;
-        za.msize = e->d_msize;
-        za.mpcap = e->d_mpcap;
-        za.list = e->d_msz_list;
-        za.list_n = e->d_msz_list_n;
-        za.mrec = e->d_mrec;
-        za.hh_key = e->d_hh_key;
-        za.hh_val = e->d_hh_val;
-        za.hh_n = e->hh_n;
-        za.ev_key = e->d_sm_key;
-        za.ev_val = e->d_sm_val;
-        za.ev_pay = e->d_sm_pay;
-        za.ev_cap = (uint32_t)e->sm_cap;
-        za.sm_ctl = e->d_sm_ctl;
-        za.map_row = e->d_map_row;
-        za.lo = lo;
-        za.lvl_at = e->d_lvl_at;
-        za.index = c->index;
-        za.err = e->d_err;
-        if (launch_map_size(za, st)) return set_err(CC_ERR_HIP, "map size launch", hipGetLastError());
-        own_lo = hi + 1;
-        if (e->szq_n) {  // this sub-batch's size / isEmpty rows join the events at their rows' positions
-          sz.szq = e->d_szq;
-          sz.szq_n = e->szq_n;
-          sz.lo = lo;
-          sz.hi = hi;
-          sz.inst = c->inst;
-          sz.op = c->op;
-          sz.index = c->index;
-          sz.inst_res = e->d_inst_res;
-          sz.res_type = e->d_res_type;
-          sz.ev_key = e->d_sm_key;
-          sz.ev_val = e->d_sm_val;
-          sz.ev_pay = e->d_sm_pay;
-          sz.cap = (uint32_t)e->sm_cap;
-          sz.ctl = e->d_sm_ctl;
-          sz.err = e->d_err;
-          sz.ttl = true;
-          if (launch_size_emit(sz, st)) return set_err(CC_ERR_HIP, "size query launch", hipGetLastError());
-        }
-        ttl_pending = true;  // (the replay answers them: after the unpermute's placeholders)
-      } else {  // exact map sizes and HashMap capacities (containsValue's iteration order)
-        MapSizeArgs za{};
-        za.ttab = e->d_ttab;
-        za.cpos = e->d_cpos;
-        za.tiles = tiles;
-        za.rows = hi - lo;
-        za.sb = e->sb_total();
-        za.k0 = e->sb;
-        za.k1 = e->sbq_base();
-        za.sb_hot = e->sb + (1u << e->map_bits);
-        za.rst_msz = e->d_rst_msz;
-        za.hot = e->d_hot;
-        za.hot_n = e->d_hot_n;
-        za.hot_len = e->d_hot_len;
-        za.hot_rpre = e->d_hot_rpre;
-        za.hot_msz = e->d_hot_msz;
-        za.res_type = e->d_res_type;
-        za.max_resources = e->cfg.max_resources;
-        za.tcnt = e->d_msz_tcnt;
-        za.msize = e->d_msize;
-        za.mpcap = e->d_mpcap;
-        za.list = e->d_msz_list;
-        za.list_n = e->d_msz_list_n;
-        za.err = e->d_err;
-        za.lvl_at = e->d_lvl_at;
-        za.index = c->index;
-        za.lo = lo;
-        if (e->small_live || e->szq_n || clr_on) {  // small / size-queried / cleared maps: their insertions / removals
-          int rc = ensure_small(e);
-          if (rc) return rc;
-          if (!c->index) return set_err(CC_ERR_INVALID, "an engine with maps needs the index column (log order)");
-          za.msmall = e->d_msmall;
-          za.mrec = e->d_mrec;
-          za.idx0 = c->index + lo;
-          za.hh_key = e->d_hh_key;
-          za.hh_val = e->d_hh_val;
-          za.hh_n = e->hh_n;
-          za.ev_key = e->d_sm_key;
-          za.ev_val = e->d_sm_val;
-          za.ev_pay = e->d_sm_pay;
-          za.ev_cap = (uint32_t)e->sm_cap;
-          za.sm_ctl = e->d_sm_ctl;
-        }
-        if (launch_map_size(za, st)) return set_err(CC_ERR_HIP, "map size launch", hipGetLastError()); DBG_SYNC("map size launch");
-        if (e->szq_n) {  // this sub-batch's size / isEmpty rows join the events
-          sz.szq = e->d_szq;
-          sz.szq_n = e->szq_n;
-          sz.lo = lo;
-          sz.hi = hi;
-          sz.inst = c->inst;
-          sz.op = c->op;
-          sz.index = c->index;
-          sz.inst_res = e->d_inst_res;
-          sz.res_type = e->d_res_type;
-          sz.ev_key = e->d_sm_key;
-          sz.ev_val = e->d_sm_val;
-          sz.ev_pay = e->d_sm_pay;
-          sz.cap = (uint32_t)e->sm_cap;
-          sz.ctl = e->d_sm_ctl;
-          sz.err = e->d_err;
-          sz.sorted_key = e->d_sm_key2;
-          sz.sorted_val = e->d_sm_val2;
-          sz.seg = e->d_sm_seg;
-          sz.nseg = e->d_sm_seg + e->cfg.max_resources;
-          sz.msize = e->d_msize;
-          sz.out_status = out->status;
-          sz.out_value = out->value;
-          if (launch_size_emit(sz, st)) return set_err(CC_ERR_HIP, "size query launch", hipGetLastError());
-        }
-        if (clr_on && launch_clr_events(ca, st)) return set_err(CC_ERR_HIP, "clear events launch", hipGetLastError());
-        if (e->small_live || e->szq_n || clr_on) {
-          uint32_t ctl[2] = {0, 0};
-          uint32_t* const p32 = reinterpret_cast<uint32_t*>(e->h_pin);  // (pinned: one round trip for both)
-          HIPCHECK(hipMemcpyAsync(p32, e->d_sm_ctl, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-          if (cv_n) HIPCHECK(hipMemcpyAsync(p32 + 2, e->d_cvev_ctl, sizeof cv_E, hipMemcpyDeviceToHost, st));
-          if (!e->coord_on) {  // (the coordination apply, launched below, writes staged results: then no early unpermute)
-            if (!e->ev_rb) HIPCHECK(hipEventCreateWithFlags(&e->ev_rb, hipEventDisableTiming));
-            HIPCHECK(hipEventRecord(e->ev_rb, st));
-            int rc = unpermute();  // (on the GPU while the host waits for the counters)
-            if (rc) return rc;
-            HIPCHECK(hipEventSynchronize(e->ev_rb));
-          } else {
-            HIPCHECK(hipStreamSynchronize(st));
-          }
-          ctl[0] = p32[0];
-          ctl[1] = p32[1];
-          if (cv_n) memcpy(&cv_E, p32 + 2, sizeof cv_E);
-          cv_known = cv_n != 0;
-          e->stat_events += ctl[0];
-          SmallArgs sa{};
-          sa.ev_key = e->d_sm_key;
-          sa.ev_key2 = e->d_sm_key2;
-          sa.ev_val = e->d_sm_val;
-          sa.ev_val2 = e->d_sm_val2;
-          sa.ev_pay = e->d_sm_pay;
-          sa.cap = (uint32_t)e->sm_cap;
-          sa.temp = e->d_sm_temp;
-          sa.temp_bytes = e->sm_temp_bytes;
-          sa.ctl = e->d_sm_ctl;
-          sa.seg = e->d_sm_seg;
-          sa.nseg = e->d_sm_seg + e->cfg.max_resources;
-          sa.cseg = e->d_sm_cseg;
-          sa.state = e->d_msm;
-          sa.big = e->d_mbig;
-          sa.msmall = e->d_msmall;
-          sa.left = e->d_msm_left + 2ull * e->cfg.max_resources;  // (on this stream: folded right after it)
-          sa.err = e->d_err;
-          sa.mpcap = e->d_mpcap;
-          sa.max_resources = e->cfg.max_resources;
-          sa.lvl_at = e->d_lvl_at;
-          sa.idx0 = c->index + lo;
-          // the replay overlaps the next sub-batch on the side stream (engine_state.h SmSet), launched once that
-          // sub-batch's partition is queued (launch_pending_replay)
-          static const bool no_side = diag_env("CC_NO_SIDE_REPLAY");  // diagnostics: the replay on the engine stream
-          if (ctl[0] && !no_side) {
-            int rc = ensure_sm_alt(e);
-            if (rc) return rc;
-            sa.defer = true;
-            sa.left = e->d_msm_left + (size_t)e->sm_cur * e->cfg.max_resources;  // (folded by wait_replay)
-          }
-          const int rs = launch_small_replay(sa, ctl[0], st, st);
-          if (sa.defer && !rs) {
-            e->pend_sa = sa;
-            e->pend = true;
-            e->pend_set = e->sm_cur;
-          }
-          if (rs) return rs == -1 ? set_err(CC_ERR_HIP, "small-map replay launch", hipGetLastError())
-                                  : set_err(CC_ERR_STATE, "small-map events exceed their buffer");
-          if (e->small_live && ctl[0] == 0 && ctl[1] == 0) e->small_live = false;  // (ctl[1]: maps small after the last replay)
-          sized = true;
-          sized_events = ctl[0];
-        }
-      }
-    }
-    if (e->coord_on) {
-      HIPCHECK(hipMemsetAsync(e->d_ev_cnt, 0, sizeof(uint16_t) * (hi - lo), st));
-      HIPCHECK(hipMemsetAsync(e->d_arena_n, 0, sizeof(unsigned long long), st));
-      CoordArgs ca{};
-      ca.xrec = e->d_xrec;
-      ca.ttab = e->d_ttab;
-      ca.tiles = tiles;
-      ca.sb = e->sb_total();
-      ca.sb_val = e->sb;
-      ca.sbq_base = e->quarter ? e->sbq_base() : 0u;
-      ca.sb_kind = e->d_sb_kind;
-      ca.res_type = e->d_res_type;
-      ca.inst_id = e->d_inst_id;
-      ca.coord = e->d_coord;
-      ca.coord_cap = e->coord_cap;
-      ca.val_meta = e->d_val_meta;
-      ca.val_v = e->d_val_v;
-      ca.rst_status = e->d_rst_status;
-      ca.rst_value = e->d_rst_value;
-      ca.ev_cnt = e->d_ev_cnt;
-      ca.arena = e->d_arena;
-      ca.arena_n = e->d_arena_n;
-      ca.arena_cap = e->arena_cap;
-      ca.leak = e->d_leak;
-      ca.leak_n = e->d_leak_n;
-      ca.leak_cap = e->leak_cap;
-      ca.err = e->d_err;
-      ca.mark = marker_of(e);
-      if (launch_apply_coord(ca, st)) return set_err(CC_ERR_HIP, "coordination apply launch", hipGetLastError()); DBG_SYNC("coordination apply launch");
-    }
-    if (!unpermuted) {
-      int rc = unpermute();
-      if (rc) return rc;
-    }
-    DBG_SYNC("unpermute launch");
-    if (cv_n) {  // in-stream containsValue answers over the unpermute's placeholders (map_cv.hip)
-      if (!cv_known) {
-        HIPCHECK(hipMemcpyAsync(e->h_pin, e->d_cvev_ctl, sizeof cv_E, hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipStreamSynchronize(st));
-        memcpy(&cv_E, e->h_pin, sizeof cv_E);
-      }
-      const int rc = launch_cv_answer(cva, cv_E, st);
-      if (rc) return rc == -2 ? set_err(CC_ERR_CAPACITY, "containsValue events exceed their buffer")
-                              : set_err(CC_ERR_HIP, "containsValue answer launch", hipGetLastError());
-    }
-    if (ttl_pending) {  // TTL mode: sizes, capacities, small maps' key sets, and the size / isEmpty rows' answers
-      int rc = ttl_replay(e, st, c->index, lo, out);
-      if (rc) return rc;
-    }
-    if (sized) {  // size / isEmpty answers over the unpermute's placeholders; then the next sub-batch's counters
-      if (e->szq_n && sized_events && launch_size_answer(sz, st))
-        return set_err(CC_ERR_HIP, "size answer launch", hipGetLastError());
-      if (clr_on && sized_events) {  // the cleared maps' sizes, capacities and size / isEmpty rows (map_clear.hip)
-        ClrReplayArgs cr{};
-        cr.key = e->d_sm_key2;
-        cr.val = e->d_sm_val2;
-        cr.pay = e->d_sm_pay;
-        cr.mflag = e->d_msmall;
-        cr.msize = e->d_msize;
-        cr.mpcap = e->d_mpcap;
-        cr.lvl_at = e->d_lvl_at;
-        cr.idx0 = c->index + lo;
-        cr.out_status = out->status;
-        cr.out_value = out->value;
-        int rc = ensure_clr_scan(e);
-        if (rc) return rc;
-        cr.scan = e->d_clr_scan;
-        cr.temp = e->d_clr_stemp;
-        cr.temp_bytes = e->clr_stemp_bytes;
-        if (launch_clr_replay(cr, sized_events, st)) return set_err(CC_ERR_HIP, "clear replay launch", hipGetLastError());
-      }
-      SmallArgs sf{};
-      sf.ctl = e->d_sm_ctl;
-      sf.msmall = e->d_msmall;
-      sf.max_resources = e->cfg.max_resources;
-      if (launch_small_finish(sf, st)) return set_err(CC_ERR_HIP, "small-map counters", hipGetLastError());
-    }
-    if (e->coord_on) {
-      EventArgs ea{};
-      ea.cpos = e->d_cpos;
-      ea.lo = lo;
-      ea.hi = hi;
-      ea.tiles = tiles;
-      ea.ev_cnt = e->d_ev_cnt;
-      ea.row_of = e->d_row_of;
-      ea.ev_loc = e->d_ev_loc;
-      ea.tile_sum = e->d_tile_sum;
-      ea.tile_off = e->d_tile_off;
-      ea.ev_total = e->d_ev_total;
-      ea.arena = e->d_arena;
-      ea.arena_n = e->d_arena_n;
-      ea.arena_cap = e->arena_cap;
-      ea.perm = e->d_ev_perm;
-      ea.bucket = e->d_ev_bucket;  // the tile-bucketed order pass (CC_EV_V1=1: the gather pass)
-      ea.ccnt = e->d_ev_ccnt;
-      if (ev) {
-        ea.out_cap = ev->capacity;
-        ea.out_pos = ev->pos;
-        ea.out_target = ev->target;
-        ea.out_code = ev->code;
-        ea.out_src = ev->src;
-        ea.out_tag = ev->tag;
-        ea.out_payload = ev->payload;
-      }
-      ea.err = e->d_err;
-      ea.mark = marker_of(e);
-      if (launch_events(ea, st)) return set_err(CC_ERR_HIP, "events launch", hipGetLastError()); DBG_SYNC("events launch");
-    }
-  }
-  {
-    int rc = join_replay(e, st);  // (barrier rows, timers and the caller read the small maps' models)
-    if (rc) return rc;
-  }
-  if (action == 2) {  // a group timer fires here (MembershipGroupState.java:92-98)
-    cc_engine::GroupTimer gt = e->gtimers[tk];
-    e->gtimers.erase(e->gtimers.begin() + (ptrdiff_t)tk);
-    const uint32_t pos = (uint32_t)(deferred ? seg_hi - 1 : seg_hi);
-    if (launch_group_fire(e->d_coord, e->coord_cap, gt.slot, gt.member, gt.tag, gt.payload, pos, e->d_ev_total, ev, e->d_err, st))
-      return set_err(CC_ERR_HIP, "group timer launch", hipGetLastError());
-    cur = seg_hi;
-    continue;
-  }
-  if (action == 0) {
-    if (e->map_bits && e->ttl_live && own_lo <= n) {  // the boundaries after the last sub-batch (manager mode: row n)
-      int rc = ttl_flush(e, c->time, n, own_lo, n, 0, st);
-      if (rc) return rc;
-    }
-    break;
-  }
-  {  // the barrier row, against the state as it stands after the rows before it
-    const uint64_t row = seg_hi;
-    ++e->stat_barriers;
-    const BarRow& br = e->bar_rows[bi];
-    const size_t bk = bi;
-    cur = row + 1;
-    ++bi;
-    if (e->map_bits && e->ttl_live) {  // the timers that fire up to this row's boundary, as size events (TtlEmit)
-      if (own_lo <= row) {
-        int rc = ttl_flush(e, c->time, n, own_lo, row, 0, st);
-        if (rc) return rc;
-      }
-      own_lo = row + 1;
-    }
-    uint32_t res = 0;
-    const uint32_t in = br.inst;
-    const uint8_t op = br.op, fl = br.flags;
-    const uint64_t a = br.a;
-    // (k_map_barriers listed the row through the device registry; the host mirror must agree before its slot
-    // indexes any per-resource array)
-    if (row >= n || in >= e->cfg.max_instances || (res = e->inst_res[in]) >= e->cfg.max_resources ||
-        !(is_keyed(e->res_type[res]) || e->res_type[res] == CC_RES_GROUP))
-      return set_err(CC_ERR_STATE, "barrier row does not resolve to a map / set / multimap / group on the host registry");
-    if (e->res_type[res] == CC_RES_GROUP) {  // schedule :86-103 (member = key, callback = a, delay = aux)
-      const uint64_t member = br.key;
-      if (launch_group_schedule(e->d_coord, e->coord_cap, res, member, row, out->status, out->value, e->d_ttl_seen, st))
-        return set_err(CC_ERR_HIP, "group schedule launch", hipGetLastError());
-      uint32_t found = 0;
-      HIPCHECK(hipMemcpyAsync(&found, e->d_ttl_seen, sizeof found, hipMemcpyDeviceToHost, st));
-      HIPCHECK(hipStreamSynchronize(st));
-      if (found) {
-        cc_engine::GroupTimer gt{};
-        gt.deadline = sched_dl[bk];
-        gt.id = ++e->gtimer_seq;
-        gt.member = member;
-        gt.tag = CC_FLAG_TAG_A(fl);
-        gt.payload = gt.tag == CC_TAG_NULL ? 0 : a;
-        gt.slot = res;
-        gt.idx = br.idx;
-        gt.fire_b = sched_fb[bk];
-        e->gtimers.push_back(gt);
-      }
-      continue;
-    }
-    MapWideArgs mw{};
-    mw.slot = res;
-    mw.op = e->res_type[res] == CC_RES_SET        ? set_as_map_op(op)
-            : e->res_type[res] == CC_RES_MULTIMAP ? mmap_as_map_op(op, CC_FLAG_TAG_A(fl))
-                                                  : op;
-    mw.atag = CC_FLAG_TAG_A(fl);
-    mw.apay = a;
-    mw.row = row;
-    mw.tbl_word = e->d_tbl_word;
-    mw.tbl_key = e->d_tbl_key;
-    mw.tbl_val = e->d_tbl_val;
-    mw.tbl_ins = e->d_tbl_ins;
-    mw.tbl_claim = e->d_tbl_claim;
-    mw.lvl_at = e->d_lvl_at;
-    if (e->ttl_live) {  // the clock at which the reference last fired timers before this row (A8)
-      uint64_t t0 = clock_before, t1 = clock_before;
-      if (c->time) {
-        t1 = std::max(br.t_row, clock_before);
-        if (row > 0) t0 = std::max(br.t_prev, clock_before);
-      }
-      mw.tbl_dl = e->d_tbl_dl;
-      mw.fire_clock = (e->cfg.flags & CC_CFG_TIMERS_DEFERRED) ? t0 : t1;
-    }
-    mw.entries = e->map_entries;
-    mw.peak_lo = e->d_mw_peak;
-    mw.dropped = e->d_mw_drop;
-    mw.cgen = e->d_mw_cgen;
-    mw.cset = e->d_cset;
-    mw.cset_n = e->cset_mask + 1;
-    mw.cset_full = e->d_cset_full;
-    mw.map_bits = e->map_bits;
-    mw.msize = e->d_msize;  // exact in both modes (TTL mode: commit + expiry events, map_small.hip)
-    mw.mpcap = e->d_mpcap;
-    mw.ctl = e->d_mw_ctl;
-    mw.small = e->res_type[res] == CC_RES_MAP ? e->d_msm : nullptr;
-    mw.big = e->d_mbig;
-    mw.hh_key = e->d_hh_key;
-    mw.hh_val = e->d_hh_val;
-    mw.hh_n = e->hh_n;
-    mw.out_status = out->status;
-    mw.out_value = out->value;
-    mw.err = e->d_err;
-    if (launch_map_wide(mw, st)) return set_err(CC_ERR_HIP, "whole-map op launch", hipGetLastError()); DBG_SYNC("whole-map op launch");
-    if (e->res_type[res] == CC_RES_MAP && (mw.op == CC_OP_MAP_CLEAR || mw.op == CC_OP_DELETE) &&
-        (launch_big_clear(e->d_mbig, e->d_msm, res, st) || launch_small_clear(e->d_msm, res, st)))
-      return set_err(CC_ERR_HIP, "small-map clear launch", hipGetLastError());
-  }
-  }
-  if (e->has_sets || e->has_mmaps) {
-    KeyedResultArgs ka{c->inst,     c->op,          c->flags, c->index,     n,           e->d_inst_res, e->d_res_type,
-                       e->cfg.max_instances, out->status, out->value, e->d_leak, e->d_leak_n, e->leak_cap, e->d_err};
-    if (launch_keyed_results(ka, st)) return set_err(CC_ERR_HIP, "set / multimap results launch", hipGetLastError()); DBG_SYNC("set / multimap results launch");
-  }
-  // Retained value commits (live.hip): after every value op of the batch has applied.  The post-pass attributes
-  // each row through the END-of-batch inst_res / res_type / val_meta: correct because the registry cannot change
-  // inside a cc_apply_batch call (resource create/delete, instance open/close are host calls that quiesce the
-  // stream between batches; no op applied on the device rebinds an instance or retypes a slot).
-  if (e->d_val_live) {
-    if (launch_value_live(c->inst, c->op, out->status, out->value, c->index, n, e->d_inst_res, e->d_res_type,
-                          e->cfg.max_instances, e->d_val_meta, e->cfg.max_resources, e->d_val_wrow, e->d_val_live, st))
-      return set_err(CC_ERR_HIP, "retained value launch", hipGetLastError());
-  }
-  if (e->coord_on && ev) HIPCHECK(hipMemcpyAsync(ev->count, e->d_ev_total, sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-  if (e->coord_on || e->map_bits) {  // the log clock (timers: lock timeouts, map TTL)
-    if (launch_clock_advance(c->time, n, 0, e->d_clock, st)) return set_err(CC_ERR_HIP, "clock", hipGetLastError()); DBG_SYNC("clock");
-  }
-  if (c->index) {  // the applied watermark = index of the batch's last entry
-    HIPCHECK(hipMemcpyAsync(e->d_last_index, c->index + (n - 1), sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-    e->applied_pending = true;
-  }
-  return CC_OK;
 }
 
 // String.hashCode of HANDLE keys (java.util.HashMap bins of MapState, MapState.java:33,49-60): merged into the host

@@ -1,7 +1,8 @@
 // engine_state.h — the engine handle (struct cc_engine) shared by the host-side translation units of
-// libcopycat_apply.so: engine.hip (lifecycle, registry, batched apply driver, readback, snapshots) and
-// manager.hip (the ResourceManager control plane, ResourceManager.java:77-264).  Host code only.
+// libcopycat_apply.so: engine.hip (lifecycle, registry, readback, snapshots), apply_batch.hip (the batched apply
+// driver) and manager.hip (the ResourceManager control plane, ResourceManager.java:77-264).  Host code only.
 #pragma once
+#include <initializer_list>
 #include <map>
 #include <set>
 #include <string>
@@ -31,6 +32,11 @@ int drain_leaks(cc_engine* e);  // the device leak log -> cc_engine::leaks
 int ckpt_save(cc_engine* e);
 int ckpt_restore(cc_engine* e);
 int ckpt_reserve(cc_engine* e);  // the checkpoint buffer, allocated before a prefix apply applies its first row
+// what engine.hip and apply_batch.hip need of each other: the profiling markers and the leak log's room (engine.hip);
+// TTL mode's expiries of the boundaries [bl, bh], or of every timer due by `adv`, as size events (apply_batch.hip)
+Marker marker_of(cc_engine* e);
+int ensure_leak(cc_engine* e, uint64_t need);
+int ttl_flush(cc_engine* e, const uint64_t* time, uint64_t n, uint64_t bl, uint64_t bh, uint64_t adv, hipStream_t st);
 
 // Occupancy bitmap of a slot space with lowest-free / highest-free search (control-plane allocation: rare, so a
 // word scan from a hint is enough).
@@ -75,7 +81,49 @@ struct SlotBits {
     if (_e != hipSuccess) return cc::set_err(CC_ERR_HIP, #x, _e);  \
   } while (0)
 
+// a step that returns an engine error code
+#define TRY(x)               \
+  do {                       \
+    int _rc = (x);           \
+    if (_rc) return _rc;     \
+  } while (0)
+
 using namespace cc;  // internal header: the engine's host translation units all work in namespace cc
+
+// One growable buffer group of the engine regrown: the old buffers freed and their pointers nulled, the capacity
+// zeroed, each buffer allocated anew, the capacity recorded.  A failed allocation leaves null pointers and a zero
+// capacity, never freed pointers.
+struct Buf {
+  void** p;
+  size_t bytes;
+};
+#define BUF(p, bytes) Buf{(void**)&(p), (size_t)(bytes)}
+template <class Cap>
+int regrow(std::initializer_list<Buf> bufs, Cap& cap, Cap want, const char* what) {
+  auto drop = [&] {
+    for (const Buf& b : bufs) {
+      if (*b.p) (void)hipFree(*b.p);
+      *b.p = nullptr;
+    }
+    cap = 0;
+  };
+  drop();
+  for (const Buf& b : bufs) {
+    const hipError_t x = hipMalloc(b.p, b.bytes);
+    if (x != hipSuccess) {
+      drop();
+      return set_err(CC_ERR_HIP, what, x);
+    }
+  }
+  cap = want;
+  return CC_OK;
+}
+template <class T>
+int alloc_once(T*& p, size_t bytes) {  // a fixed-size buffer, on first need
+  if (p) return CC_OK;
+  const hipError_t x = hipMalloc((void**)&p, bytes);
+  return x == hipSuccess ? CC_OK : set_err(CC_ERR_HIP, "hipMalloc (buffer on first need)", x);
+}
 
 struct cc_engine {
   uint32_t coord_cap = 64;  // entries per coordination block (cc_config.coord_cap, a power of two)
@@ -178,9 +226,8 @@ struct cc_engine {
   uint64_t cset_mask = 0;          // set entries - 1
   uint32_t* d_cset_full = nullptr; // the set overflowed
   uint64_t* d_tbl_claim = nullptr; // [map_entries] log index at which each entry was first bound
-  unsigned long long* d_lvl_at = nullptr;
-  uint64_t* d_half_count = nullptr;
-  EvPay* d_sm_pay = nullptr;       // [sm_cap] map event payloads by emission slot (map_small.hip)  // a batch applied as two calls (kBarCap): the second call's event count  // [max_resources * kLvlSlots] capacity-level timeline (common.h)
+  unsigned long long* d_lvl_at = nullptr;  // [max_resources * kLvlSlots] capacity-level timeline (common.h)
+  uint64_t* d_half_count = nullptr;  // a batch applied as two calls (kBarCap): the second call's event count
   // exact map sizes / HashMap capacities (map_wide.hip launch_map_size; not in TTL mode)
   uint32_t* d_rst_msz = nullptr;   // [sub_batch + 4 kPT] each region map commit's map and size change, staging order
   uint32_t* d_hot_msz = nullptr;   // hot-key commits' size changes (HotArgs::hot_msz)
@@ -198,11 +245,9 @@ struct cc_engine {
   uint8_t* d_msm_left = nullptr;   // [3][max_resources] maps a replay saw leave the window: sets 0 / 1 (side-stream
                                    // replays), 2 (engine-stream replays); folded into d_msmall on the engine stream
   uint32_t* d_sm_ctl = nullptr;    // [4] events of the sub-batch, maps still in the window
-  uint64_t *d_sm_key = nullptr, *d_sm_key2 = nullptr;  // [sm_cap] map events (small / size-queried maps; TTL mode: all)
-  uint32_t *d_sm_val = nullptr, *d_sm_val2 = nullptr;
   uint32_t* d_sm_seg = nullptr;    // [max_resources + 1] run starts + count
   uint32_t* d_cvbloom = nullptr;  // the in-stream containsValue operands' filter (common.h CvCtx)
-  uint32_t* d_sm_cseg = nullptr;  // the replayed events without implied chain events: runs, counts (map_small.hip)
+  // The map event buffers (small / size-queried maps; TTL mode: all), as a set: `sm` is the current one.
   // Outside TTL mode the small-map replay of sub-batch i runs on a side stream while sub-batch i + 1 runs on the
   // engine's: the event buffers alternate between two sets (swapped at each sub-batch start), a set is reused only
   // after its replay finished (ev_rep), and the engine stream waits for the side stream before barrier rows, timers
@@ -212,11 +257,16 @@ struct cc_engine {
   // engine-stream reader of mpcap inside a sub-batch, k_msize_scan, loads it atomically); every wait for a replay
   // (wait_replay) is followed on the engine stream by the fold of its marks into the d_msmall snapshot.
   struct SmSet {
-    uint64_t *key = nullptr, *key2 = nullptr;
+    uint64_t *key = nullptr, *key2 = nullptr;  // [sm_cap] the events, and their sorted copies
     uint32_t *val = nullptr, *val2 = nullptr;
-    EvPay* pay = nullptr;
-    uint32_t* cseg = nullptr;
-  } sm_alt;
+    EvPay* pay = nullptr;      // [sm_cap] payloads by emission slot (map_small.hip)
+    uint32_t* cseg = nullptr;  // the replayed events without implied chain events: runs, counts (map_small.hip)
+    void release() {
+      for (void* p : {(void*)key, (void*)key2, (void*)val, (void*)val2, (void*)pay, (void*)cseg})
+        if (p) (void)hipFree(p);
+      *this = SmSet{};
+    }
+  } sm, sm_alt;
   bool sm_alt_on = false;
   hipStream_t side_st = nullptr;
   hipEvent_t ev_prep = nullptr, ev_rep[2] = {nullptr, nullptr};
@@ -235,7 +285,7 @@ struct cc_engine {
   size_t clr_scan_cap = 0, clr_stemp_bytes = 0;
   uint8_t* d_clr_btab = nullptr;  // [R][nb] clear epochs per row bucket (common.h ClrCtx)
   size_t clr_btab_bytes = 0;
-  uint64_t sm_cap = 0;             // events the buffers hold (engine.hip small_cap_needed)
+  uint64_t sm_cap = 0;             // events the buffers hold (apply_batch.hip small_cap_needed)
   bool small_live = false;         // some map may still be in the window (the host then reads the event count)
   // map size / isEmpty rows answered in the stream (outside TTL mode; map_small.hip k_size_answer)
   uint32_t* d_szq = nullptr;       // [szq_cap] the batch's size / isEmpty rows
@@ -288,9 +338,9 @@ struct cc_engine {
   uint32_t* d_map_row = nullptr;   // [sub_batch] staging position -> batch row
   uint32_t* d_ttl_seen = nullptr;
   bool ttl_live = false;
-  bool has_sets = false;
+  bool has_sets = false;    // SetState resources share the map table (results rewritten by k_set_results)
   bool has_values = false;  // an AtomicValueState resource was ever created (else k_apply_value is not launched)
-  bool has_mmaps = false;  // MultiMapState resources share the map table too (every Put lands in the leak log)  // SetState resources share the map table (results rewritten by k_set_results)
+  bool has_mmaps = false;   // MultiMapState resources share the map table too (every Put lands in the leak log)
   // MembershipGroupState.schedule timers (MembershipGroupState.java:86-103): armed by schedule barrier rows, fired
   // at the batch boundary where the reference's fire_due runs (host-ordered by (deadline, id))
   struct GroupTimer {
