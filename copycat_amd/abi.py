@@ -242,6 +242,52 @@ class cc_wire_out(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("inst", "iid", "op", "flags", "key", "a", "b", "aux", "kind")]
 
 
+# packed host batches (include/copycat_apply.h "packed host batches"; copycat_amd/csrc/pack.cpp, unpack.hip)
+CC_PACK_BLOCK_ROWS = 4096
+CC_PACK_VERSION = 1
+CC_PACK_MAGIC = 1263551299
+CC_PACK_COLUMNS = 9
+CC_PK_FOR = 0
+CC_PK_REL_A = 1
+CC_PACKED_TIMELINE = 1
+
+
+class cc_pack_header(C.Structure):
+    _fields_ = [
+        ("magic", C.c_uint32),
+        ("version", C.c_uint32),
+        ("n", C.c_uint64),
+        ("blocks", C.c_uint64),
+        ("bytes", C.c_uint64),
+        ("present", C.c_uint32),
+        ("block_rows", C.c_uint32),
+        ("reserved", C.c_uint64 * 3),
+    ]
+
+
+class cc_pack_col(C.Structure):
+    _fields_ = [
+        ("mode", C.c_uint8),
+        ("width", C.c_uint8),
+        ("reserved16", C.c_uint16),
+        ("offset", C.c_uint32),
+        ("base", C.c_uint64),
+    ]
+
+
+class cc_pack_block(C.Structure):
+    _fields_ = [("rows", C.c_uint32), ("bytes", C.c_uint32), ("offset", C.c_uint64), ("col", cc_pack_col * 9)]
+
+
+class cc_packed_opts(C.Structure):
+    _fields_ = [
+        ("chunk_rows", C.c_uint64),
+        ("flags", C.c_uint32),
+        ("reserved32", C.c_uint32),
+        ("reserved", C.c_uint64 * 2),
+    ]
+
+
 BATCH_COLUMNS = (
     ("index", "u8"),
     ("time", "u8"),

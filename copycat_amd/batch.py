@@ -47,6 +47,109 @@ class Batch:
         return {name: getattr(self, name) for name, _ in abi.BATCH_COLUMNS}
 
 
+def _pack_lib():
+    from .engine import lib  # (the packed-batch calls live in the engine library; no device is touched)
+
+    return lib()
+
+
+def _pack_fail(rc):
+    from .engine import EngineError
+
+    raise EngineError(rc, _pack_lib().cc_last_error().decode(errors="replace"))
+
+
+def _aligned_bytes(n, align=64):
+    buf = np.zeros(n + align, np.uint8)
+    off = (-buf.ctypes.data) % align
+    return buf[off:off + n]
+
+
+def pack(b, columns=None, threads=0, out=None):
+    """cc_pack_batch: the batch's columns (all nine, or those named in `columns`; the others are absent, the NULL
+    column pointers of cc_batch) as one packed blob, a 16-byte-aligned uint8 array.  `out`: a 16-byte-aligned uint8
+    buffer to pack into (e.g. page-locked once and reused); the result is then a view of it."""
+    import ctypes as C
+
+    L = _pack_lib()
+    n = len(b)
+    s = abi.cc_batch()
+    present = 0
+    keep = []  # (the contiguous columns, alive across the call)
+    for c, (name, dt) in enumerate(abi.BATCH_COLUMNS):
+        if columns is None or name in columns:
+            arr = np.ascontiguousarray(getattr(b, name), dtype=np.dtype(dt))
+            keep.append(arr)
+            setattr(s, name, arr.ctypes.data)
+            present |= 1 << c
+    blob = out
+    if blob is None:
+        bound = C.c_uint64()
+        rc = L.cc_pack_bound(n, present, C.byref(bound))
+        if rc:
+            _pack_fail(rc)
+        blob = _aligned_bytes(bound.value)
+    size = C.c_uint64()
+    rc = L.cc_pack_batch(C.byref(s), n, blob.ctypes.data, blob.nbytes, threads, C.byref(size))
+    if rc:
+        _pack_fail(rc)
+    return blob[:size.value]
+
+
+def pack_check(blob):
+    """cc_pack_check: (n, present mask) of a well-formed blob; raises EngineError (CC_ERR_INVALID) otherwise."""
+    import ctypes as C
+
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    n, present = C.c_uint64(), C.c_uint32()
+    rc = _pack_lib().cc_pack_check(blob.ctypes.data, blob.nbytes, C.byref(n), C.byref(present))
+    if rc:
+        _pack_fail(rc)
+    return n.value, present.value
+
+
+def unpack(blob, threads=0):
+    """cc_unpack_batch: the host decoder.  Absent columns come back as zeros (see pack_check for the mask)."""
+    import ctypes as C
+
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    n, present = pack_check(blob)
+    b = Batch(n)
+    s = abi.cc_batch_out()
+    for c, (name, _) in enumerate(abi.BATCH_COLUMNS):
+        if (present >> c) & 1:
+            setattr(s, name, getattr(b, name).ctypes.data)
+    rc = _pack_lib().cc_unpack_batch(blob.ctypes.data, blob.nbytes, C.byref(s), threads)
+    if rc:
+        _pack_fail(rc)
+    return b
+
+
+def pack_info(blob):
+    """The directory of a packed blob: {"n", "blocks", "bytes", "present", "bytes_per_row", "columns": {name:
+    {"rows": {(mode, width): rows}, "bytes_per_row": packed bytes per row, "blocks": [(mode, width, base), ...]}}}."""
+    import ctypes as C
+
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    n, present = pack_check(blob)
+    hd = abi.cc_pack_header.from_buffer_copy(blob[:C.sizeof(abi.cc_pack_header)].tobytes())
+    lo = C.sizeof(abi.cc_pack_header)
+    dir_ = (abi.cc_pack_block * hd.blocks).from_buffer_copy(blob[lo:lo + hd.blocks * C.sizeof(abi.cc_pack_block)].tobytes())
+    cols = {}
+    for c, (name, _) in enumerate(abi.BATCH_COLUMNS):
+        if not (present >> c) & 1:
+            continue
+        rows, blocks, size = {}, [], 0
+        for blk in dir_:
+            e = blk.col[c]
+            rows[(e.mode, e.width)] = rows.get((e.mode, e.width), 0) + blk.rows
+            blocks.append((e.mode, e.width, e.base))
+            size += blk.rows * e.width
+        cols[name] = {"rows": rows, "blocks": blocks, "bytes_per_row": size / n if n else 0.0}
+    return {"n": n, "blocks": hd.blocks, "bytes": hd.bytes, "present": present,
+            "bytes_per_row": hd.bytes / n if n else 0.0, "columns": cols}
+
+
 def tagged(v):
     """Python value -> canonical (tag, payload).  None -> NULL; bool -> BOOL; int -> LONG.
 

@@ -118,6 +118,11 @@ static void free_all(cc_engine* e) {
   e->sm_alt.release();
   for (hipEvent_t ev : {e->ev_prep, e->ev_rep[0], e->ev_rep[1], e->ev_rb})
     if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : {e->pk_landed[0], e->pk_landed[1], e->pk_drained[0], e->pk_drained[1]})
+    if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : e->pk_stamp) (void)hipEventDestroy(ev);
+  for (hipStream_t s : {e->pk_in, e->pk_out})
+    if (s) (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s);
   if (e->side_st) (void)hipStreamDestroy(e->side_st);
   if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
 }

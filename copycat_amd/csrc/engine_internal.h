@@ -717,4 +717,25 @@ struct RetainedArgs {
 };
 int launch_retained(const RetainedArgs& a, hipStream_t st);
 
+// Packed host batch -> wide columns (unpack.hip): block k of `dir` decodes into rows [4096 k, ...) of the columns.
+// `data` holds the blob's bytes from blob offset `data_base` (a multiple of 16) on; both are device copies of a blob
+// that passed cc_pack_check.
+struct UnpackArgs {
+  const cc_pack_block* dir;
+  const uint8_t* data;
+  uint64_t data_base;
+  uint64_t* index;
+  uint64_t* time;
+  uint32_t* inst;
+  uint8_t* op;
+  uint8_t* flags;
+  uint64_t* key;
+  uint64_t* a;
+  uint64_t* b;
+  uint64_t* aux;
+  uint32_t present;
+};
+int launch_unpack(const UnpackArgs& a, uint32_t blocks, hipStream_t st);
+int pack_err(int code, const char* what);  // pack.cpp's route to cc_last_error
+
 }  // namespace cc

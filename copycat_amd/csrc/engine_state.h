@@ -406,8 +406,14 @@ struct cc_engine {
   uint64_t px_bcnt_cap = 0;
   uint64_t* d_px_evn = nullptr;
   // device staging of the host-memory entry points (host_path.hip): grown on demand, kept between calls
-  void* hw_buf[24] = {};
-  size_t hw_cap[24] = {};
+  void* hw_buf[32] = {};
+  size_t hw_cap[32] = {};
+  // cc_apply_batch_host_packed's pipeline (host_path.hip; created by its first call): the copy-in and copy-out streams,
+  // "piece k landed" / "result set k copied out" per buffer, and the per-chunk stage stamps of its timeline
+  hipStream_t pk_in = nullptr, pk_out = nullptr;
+  hipEvent_t pk_landed[2] = {}, pk_drained[2] = {};
+  std::vector<hipEvent_t> pk_stamp;  // 8 per chunk of the last call: H2D, decode, apply, D2H begin / end
+  uint64_t pk_chunks = 0;            // chunks of the last call whose stamps are all recorded
   // per-kernel profiling (cc_profile_enable)
   bool prof_on = false;
   std::vector<hipEvent_t> ev_pool;

@@ -35,7 +35,7 @@ enum HwSlot : int {
   kHwBitmap,
   kHwNum
 };
-static_assert(kHwNum <= 24, "cc_engine::hw_buf");
+static_assert(kHwNum <= 32, "cc_engine::hw_buf");
 
 // Device buffer `slot` with room for `bytes` (the previous contents are not kept).  The callers are synchronous, so
 // no launch of an earlier call still reads a buffer that is replaced here.
@@ -480,7 +480,7 @@ struct HostPrefix : PrefixPath {
 
 // ---- device-resident columns (cc_apply_batch_prefix): results and events stay in HBM ---------------------------------
 enum PxSlot : int { kHwSaveStatus = kHwNum, kHwSaveValue, kPxSlots };
-static_assert(kPxSlots <= 24, "cc_engine::hw_buf");
+static_assert(kPxSlots <= 32, "cc_engine::hw_buf");
 
 struct DevicePrefix : PrefixPath {
   cc_engine* e;
@@ -701,6 +701,248 @@ extern "C" int cc_apply_batch_prefix(cc_engine* e, const cc_batch* c, uint64_t n
   if (ev && !e->d_px_evn) HIPCHECK(hipMalloc(&e->d_px_evn, sizeof(uint64_t)));
   DevicePrefix p(e, c, n, out, ev, stream, st);
   return prefix_flow(e, n, e->map_bits != 0 || ev != nullptr, p, h_applied);
+}
+
+// ---- packed host batches (pack.cpp, unpack.hip) -----------------------------------------------------------------------
+// cc_apply_batch_host_packed is the three-stage pipeline of a PCIe-inclusive step, inside the library:
+//
+//   copy-in  (pk_in)      | H2D 0 | H2D 1 |   H2D 2   |   H2D 3   |
+//   engine   (own_stream)         | dec 0 + apply 0 | dec 1 + apply 1 | dec 2 + apply 2 | ...
+//   copy-out (pk_out)                               |   D2H 0   |     |   D2H 1   |
+//
+// A chunk is a run of whole blocks; its piece of the blob (its directory entries, then its blocks' data areas, which
+// are contiguous because offsets ascend with the block number) goes into one of two piece buffers.  The H2D of chunk
+// k + 1 is enqueued BEFORE cc_apply_batch of chunk k is called: on an engine with maps that call syncs the host, and
+// the copy must already be in flight.  Decode and apply share the engine's stream, so one decoded column set is
+// enough; there are two result sets, each copied out straight into the caller's rows [lo, hi) while the next chunk
+// is applied.  The host waits for each chunk's device-side checks (cc_sync) before it applies the next one: that is
+// what "stop at the first failing chunk" costs, one round trip per chunk of up to 16 Mi rows.
+namespace {
+
+enum PkSlot : int { kHwBlob0 = kPxSlots, kHwBlob1, kHwStatus1, kHwValue1, kPkSlots };
+static_assert(kPkSlots <= 32, "cc_engine::hw_buf");
+constexpr uint32_t kPkNeed = 4 | 8 | 16 | 64 | 128;  // inst, op, flags, a, b: the columns cc_apply_batch requires
+constexpr size_t kPkEsz[9] = {8, 8, 4, 1, 1, 8, 8, 8, 8};
+
+int pk_init(cc_engine* e) {
+  if (!e->pk_in) HIPCHECK(hipStreamCreateWithFlags(&e->pk_in, hipStreamNonBlocking));
+  if (!e->pk_out) {
+    // The copy-out stream is created at the highest stream priority: the runtime maps a process's streams onto a few
+    // hardware queues per priority level (4 by default), and at equal priority the two copy streams landed on one
+    // queue, which ran H2D and D2H one after the other (measured: the call took the SUM of the two directions).
+    int least = 0, greatest = 0;
+    HIPCHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIPCHECK(hipStreamCreateWithPriority(&e->pk_out, hipStreamNonBlocking, greatest));
+  }
+  for (hipEvent_t* ev : {&e->pk_landed[0], &e->pk_landed[1], &e->pk_drained[0], &e->pk_drained[1]})
+    if (!*ev) HIPCHECK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+  return CC_OK;
+}
+
+int host_events_ok(const cc_events* h) {
+  if (h && (!h->count || (h->capacity && (!h->pos || !h->target || !h->code || !h->src || !h->tag || !h->payload))))
+    return set_err(CC_ERR_INVALID, "host event stream: null column or count");
+  return CC_OK;
+}
+
+UnpackArgs unpack_args(const void* d_dir, const void* d_data, uint64_t data_base, void* const* col, uint32_t present) {
+  UnpackArgs a{};
+  a.dir = (const cc_pack_block*)d_dir;
+  a.data = (const uint8_t*)d_data;
+  a.data_base = data_base;
+  a.index = (uint64_t*)col[0], a.time = (uint64_t*)col[1], a.inst = (uint32_t*)col[2], a.op = (uint8_t*)col[3];
+  a.flags = (uint8_t*)col[4], a.key = (uint64_t*)col[5], a.a = (uint64_t*)col[6], a.b = (uint64_t*)col[7];
+  a.aux = (uint64_t*)col[8];
+  a.present = present;
+  return a;
+}
+
+}  // namespace
+
+extern "C" int cc_unpack_to_device(cc_engine* e, const void* h_blob, uint64_t bytes, const cc_batch_out* d_cols,
+                                   void* stream) {
+  if (!e || !d_cols) return set_err(CC_ERR_INVALID, "null argument");
+  uint64_t n = 0;
+  uint32_t present = 0;
+  TRY(cc_pack_check(h_blob, bytes, &n, &present));  // (a malformed blob never reaches the GPU)
+  if (n == 0) return CC_OK;
+  void* const col[9] = {d_cols->index, d_cols->time, d_cols->inst, d_cols->op, d_cols->flags,
+                        d_cols->key,   d_cols->a,    d_cols->b,    d_cols->aux};
+  for (int c = 0; c < 9; ++c)
+    if (((present >> c) & 1) && (!col[c] || ((uintptr_t)col[c] & 15)))
+      return set_err(CC_ERR_INVALID, "unpack: a present column's device pointer is null or not 16-byte aligned");
+  HIPCHECK(hipSetDevice(e->device));
+  const cc_pack_header* hd = (const cc_pack_header*)h_blob;
+  if (hd->blocks > 0x7FFFFFFFull) return set_err(CC_ERR_CAPACITY, "unpack: more than 2^31 blocks");
+  void* d = nullptr;
+  TRY(hw(e, kHwBlob0, hd->bytes, &d));
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHECK(hipMemcpyAsync(d, h_blob, hd->bytes, hipMemcpyHostToDevice, st));
+  if (launch_unpack(unpack_args((const uint8_t*)d + sizeof *hd, d, 0, col, present), (uint32_t)hd->blocks, st))
+    return set_err(CC_ERR_HIP, "unpack launch", hipGetLastError());
+  return CC_OK;
+}
+
+extern "C" int cc_apply_batch_host_packed(cc_engine* e, const void* h_blob, uint64_t bytes, const cc_results* hout,
+                                          const cc_events* hev, const cc_packed_opts* opts, uint64_t* h_rows_done) {
+  if (h_rows_done) *h_rows_done = 0;
+  if (!e || !hout) return set_err(CC_ERR_INVALID, "null argument");
+  if (opts && (opts->flags & ~(uint32_t)CC_PACKED_TIMELINE)) return set_err(CC_ERR_INVALID, "packed apply: unknown flag");
+  uint64_t n = 0;
+  uint32_t present = 0;
+  TRY(cc_pack_check(h_blob, bytes, &n, &present));  // (before anything is copied or launched)
+  TRY(host_events_ok(hev));
+  if (n && (!hout->status || !hout->value)) return set_err(CC_ERR_INVALID, "null argument");
+  HIPCHECK(hipSetDevice(e->device));
+  e->pk_chunks = 0;
+  if (n == 0) {
+    if (hev) *hev->count = 0;
+    return CC_OK;
+  }
+  if ((present & kPkNeed) != kPkNeed)
+    return set_err(CC_ERR_INVALID, "inst/op/flags/a/b columns and status/value outputs are required");
+  e->last_err_bits = 0;
+  hipStream_t st = e->own_stream;
+  if (st != e->last_stream) HIPCHECK(hipStreamSynchronize(e->last_stream));
+  e->last_stream = st;
+  TRY(pk_init(e));
+
+  const uint64_t kB = CC_PACK_BLOCK_ROWS;
+  uint64_t chunk = opts && opts->chunk_rows ? opts->chunk_rows : (16ull << 20);
+  chunk = std::min<uint64_t>(chunk, 1ull << 40);
+  chunk = (chunk + kB - 1) / kB * kB;
+  // whole blocks within max_batch and one extended sub-batch (an engine smaller than a block takes a block: a batch
+  // larger than max_batch then fails as it does in cc_apply_batch)
+  const uint64_t cap_rows = std::max<uint64_t>(std::min(e->cfg.max_batch, e->sub_ext) / kB * kB, kB);
+  chunk = std::min(chunk, cap_rows);
+  const uint64_t bpc = chunk / kB, nchunks = (n + chunk - 1) / chunk;
+  const bool ck = e->map_bits != 0 || hev != nullptr;  // as the parts of cc_apply_batch_host_prefix
+  if (ck) TRY(ckpt_reserve(e));
+  const bool stamps = opts && (opts->flags & CC_PACKED_TIMELINE);
+  if (stamps)
+    while (e->pk_stamp.size() < 8 * nchunks) {
+      hipEvent_t ev;
+      HIPCHECK(hipEventCreate(&ev));
+      e->pk_stamp.push_back(ev);
+    }
+  auto stamp = [&](uint64_t k, int which, hipStream_t s) -> hipError_t {
+    return stamps ? hipEventRecord(e->pk_stamp[8 * k + which], s) : hipSuccess;
+  };
+
+  const cc_pack_header* hd = (const cc_pack_header*)h_blob;
+  const uint8_t* const blob = (const uint8_t*)h_blob;
+  const cc_pack_block* const dir = (const cc_pack_block*)(blob + sizeof *hd);
+  void* piece[2] = {};
+  uint64_t piece_base[2] = {}, piece_dir[2] = {};
+  // chunk k's piece on its way: directory entries, then the data areas of its blocks
+  auto send = [&](uint64_t k) -> int {
+    const uint64_t b0 = k * bpc, b1 = std::min(hd->blocks, b0 + bpc);
+    const uint64_t lo = dir[b0].offset, hi = dir[b1 - 1].offset + dir[b1 - 1].bytes, db = (b1 - b0) * sizeof(cc_pack_block);
+    void* p = nullptr;
+    TRY(hw(e, kHwBlob0 + (int)(k & 1), db + (hi - lo), &p));
+    HIPCHECK(stamp(k, 0, e->pk_in));
+    HIPCHECK(hipMemcpyAsync(p, dir + b0, db, hipMemcpyHostToDevice, e->pk_in));
+    if (hi > lo) HIPCHECK(hipMemcpyAsync((uint8_t*)p + db, blob + lo, hi - lo, hipMemcpyHostToDevice, e->pk_in));
+    HIPCHECK(stamp(k, 1, e->pk_in));
+    HIPCHECK(hipEventRecord(e->pk_landed[k & 1], e->pk_in));
+    piece[k & 1] = p, piece_base[k & 1] = lo, piece_dir[k & 1] = db;
+    return CC_OK;
+  };
+  uint64_t ev_n = 0;  // events of the chunks so far (the failing chunk's included)
+  // every stream drained before the call returns: a copy in flight reads the caller's blob or writes its result rows
+  auto leave = [&](int rc) {
+    (void)hipStreamSynchronize(e->pk_in);
+    (void)hipStreamSynchronize(e->pk_out);
+    if (hev) *hev->count = ev_n;
+    return rc;
+  };
+  int rc = send(0);
+  if (rc) return leave(rc);
+  for (uint64_t k = 0; k < nchunks; ++k) {
+    const uint64_t lo = k * chunk, hi = std::min(n, lo + chunk), m = hi - lo;
+    const int s = (int)(k & 1);
+    if (k + 1 < nchunks && (rc = send(k + 1))) return leave(rc);
+    // decode: the wide columns of rows [lo, hi)
+    void* dcol[9] = {};
+    for (int c = 0; c < 9; ++c)
+      if (((present >> c) & 1) && (rc = hw(e, kHwCol + c, kPkEsz[c] * m, &dcol[c]))) return leave(rc);
+    void *d_status, *d_value;
+    if ((rc = hw(e, s ? kHwStatus1 : kHwStatus, m, &d_status)) || (rc = hw(e, s ? kHwValue1 : kHwValue, 8 * m, &d_value)))
+      return leave(rc);
+    hipError_t x = hipStreamWaitEvent(st, e->pk_landed[s], 0);
+    if (x == hipSuccess) x = stamp(k, 2, st);
+    if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: wait for the piece", x));
+    if (launch_unpack(unpack_args(piece[s], (const uint8_t*)piece[s] + piece_dir[s], piece_base[s], dcol, present),
+                      (uint32_t)((m + kB - 1) / kB), st))
+      return leave(set_err(CC_ERR_HIP, "unpack launch", hipGetLastError()));
+    x = stamp(k, 3, st);
+    // result set s: its copy-out of chunk k - 2 is done before it is prefilled again (sentinels as in apply_host)
+    if (x == hipSuccess && k >= 2) x = hipStreamWaitEvent(st, e->pk_drained[s], 0);
+    if (x == hipSuccess) x = hipMemsetAsync(d_status, 0xFF, m, st);
+    if (x == hipSuccess) x = hipMemsetAsync(d_value, 0xA5, 8 * m, st);
+    if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: result prefill", x));
+    // the chunk's events are appended to the host stream from the events so far on
+    uint64_t cnt = 0;
+    cc_events v{}, dev{};
+    if (hev) {
+      v = *hev;
+      const uint64_t used = std::min(ev_n, hev->capacity);
+      v.pos += used, v.target += used, v.code += used, v.src += used, v.tag += used, v.payload += used;
+      v.capacity -= used;
+      v.count = &cnt;
+    }
+    if ((rc = hw_events(e, hev ? &v : nullptr, &dev))) return leave(rc);
+    if (ck && (rc = ckpt_save(e))) return leave(rc);
+    const cc_batch d{(const uint64_t*)dcol[0], (const uint64_t*)dcol[1], (const uint32_t*)dcol[2],
+                     (const uint8_t*)dcol[3],  (const uint8_t*)dcol[4],  (const uint64_t*)dcol[5],
+                     (const uint64_t*)dcol[6], (const uint64_t*)dcol[7], (const uint64_t*)dcol[8]};
+    const cc_results r{(uint8_t*)d_status, (uint64_t*)d_value};
+    (void)stamp(k, 4, st);
+    e->last_err_bits = 0;
+    rc = cc_apply_batch(e, &d, m, &r, hev ? &dev : nullptr, st);
+    if (rc) {
+      (void)hipStreamSynchronize(st);
+      return leave(rc);
+    }
+    (void)stamp(k, 5, st);
+    const int rs = cc_sync(e);  // device-side checks (capacity, unsupported ops, time order); the stream is drained
+    const int re = hw_events_back(e, hev ? &v : nullptr, &dev);
+    for (uint64_t i = 0; hev && lo && i < std::min(cnt, v.capacity); ++i) v.pos[i] += (uint32_t)lo;
+    ev_n += cnt;
+    rc = rs ? rs : re;
+    bool rolled_back = false;
+    if (rc == CC_ERR_CAPACITY && ck) {  // a full event stream or map table region, and nothing else: not applied
+      const uint32_t bits = e->last_err_bits;
+      if (bits && !(bits & ~(kErrCapacity | kErrEvents))) {
+        const int rr = ckpt_restore(e);
+        if (rr) return leave(rr);
+        e->last_err_bits = bits;
+        rolled_back = true;
+      }
+    }
+    if (!rolled_back) {  // (a failing chunk that stays applied returns its rows, as cc_apply_batch_host does)
+      x = stamp(k, 6, e->pk_out);
+      if (x == hipSuccess) x = hipMemcpyAsync(hout->status + lo, d_status, m, hipMemcpyDeviceToHost, e->pk_out);
+      if (x == hipSuccess) x = hipMemcpyAsync(hout->value + lo, d_value, 8 * m, hipMemcpyDeviceToHost, e->pk_out);
+      if (x == hipSuccess) x = stamp(k, 7, e->pk_out);
+      if (x == hipSuccess) x = hipEventRecord(e->pk_drained[s], e->pk_out);
+      if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: result copy-out", x));
+    }
+    if (rc) return leave(rc);
+    if (h_rows_done) *h_rows_done = hi;
+    e->pk_chunks = stamps ? k + 1 : 0;
+  }
+  return leave(CC_OK);
+}
+
+extern "C" int cc_packed_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms) {
+  if (!e || !chunks || (cap && !h_ms)) return set_err(CC_ERR_INVALID, "null argument");
+  HIPCHECK(hipSetDevice(e->device));
+  *chunks = e->pk_chunks;
+  for (uint64_t k = 0; k < std::min(cap, e->pk_chunks); ++k)
+    for (int j = 0; j < 4; ++j)
+      HIPCHECK(hipEventElapsedTime(h_ms + 4 * k + j, e->pk_stamp[8 * k + 2 * j], e->pk_stamp[8 * k + 2 * j + 1]));
+  return CC_OK;
 }
 
 extern "C" int cc_sessions_close_host(cc_engine* e, const uint64_t* h_clients, uint64_t count, const cc_events* h_events,

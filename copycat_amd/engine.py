@@ -108,6 +108,15 @@ def lib():
             "cc_apply_batch_host_prefix": (i32, [P, P, u64, P, P, P]),
             "cc_apply_batch_prefix": (i32, [P, P, u64, P, P, P, P]),
             "cc_merge_results": (i32, [P, u64, P, u32, u32, u32, P, P]),
+            "cc_pack_bound": (i32, [u64, u32, P]),
+            "cc_pack_batch": (i32, [P, u64, P, u64, u32, P]),
+            "cc_pack_check": (i32, [P, u64, P, P]),
+            "cc_unpack_batch": (i32, [P, u64, P, u32]),
+            "cc_unpack_to_device": (i32, [P, P, u64, P, P]),
+            "cc_apply_batch_host_packed": (i32, [P, P, u64, P, P, P, P]),
+            "cc_packed_timeline": (i32, [P, u64, P, P]),
+            "cc_host_register": (i32, [P, u64]),
+            "cc_host_unregister": (i32, [P]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -387,6 +396,53 @@ class Engine:
             _check(rc)
         return applied.value
 
+    def apply_host_packed(self, blob, n, capacity=None, chunk_rows=0, events=True, out=None, timeline=False):
+        """cc_apply_batch_host_packed: a packed blob (batch.pack) of n rows in, host results and events out, pipelined in
+        chunks of `chunk_rows` rows (0 = 16 Mi).  Returns (status, value, events, rows_done): what apply_host_events
+        returns plus the rows of the chunks fully applied (n on success).  A call that stops at a chunk on a capacity
+        returns normally with rows_done < n (events["count"] then includes the failing chunk's events); any other
+        failure raises.  events=False: no event stream (as apply_host; the third value is None).  `out`: (status,
+        value) numpy arrays to write into (e.g. page-locked with host_register)."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        status, value = out if out is not None else (np.full(n, RESULT_SENTINEL, np.uint8), np.zeros(n, np.uint64))
+        r = abi.cc_results(status.ctypes.data, value.ctypes.data)
+        opts = abi.cc_packed_opts(chunk_rows=chunk_rows, flags=abi.CC_PACKED_TIMELINE if timeline else 0)
+        done = C.c_uint64()
+        ev, cols, count = None, None, np.zeros(1, np.uint64)
+        if events:
+            cap = capacity if capacity is not None else max(4 * n, 1024)
+            cols = {"pos": np.zeros(cap, np.uint32), "target": np.zeros(cap, np.uint32), "code": np.zeros(cap, np.uint8),
+                    "src": np.zeros(cap, np.uint8), "tag": np.zeros(cap, np.uint8), "payload": np.zeros(cap, np.uint64)}
+            ev = abi.cc_events(*(cols[k].ctypes.data for k in ("pos", "target", "code", "src", "tag", "payload")), cap,
+                               count.ctypes.data)
+        rc = self.L.cc_apply_batch_host_packed(self.h, blob.ctypes.data, blob.nbytes, C.byref(r),
+                                               C.byref(ev) if ev is not None else None, C.byref(opts), C.byref(done))
+        if rc != abi.CC_OK and not (rc == abi.CC_ERR_CAPACITY and done.value < n):
+            _check(rc)
+        evs = None
+        if events:
+            m = int(min(count[0], cap))
+            evs = {k: v[:m] for k, v in cols.items()}
+            evs["count"] = int(count[0])
+        return status, value, evs, done.value
+
+    def packed_timeline(self):
+        """Per chunk of the last apply_host_packed(timeline=True): (H2D, decode, apply, D2H) milliseconds."""
+        n = C.c_uint64()
+        _check(self.L.cc_packed_timeline(self.h, 0, C.byref(n), None))
+        ms = np.zeros((max(n.value, 1), 4), np.float32)
+        _check(self.L.cc_packed_timeline(self.h, n.value, C.byref(n), _np(ms)))
+        return ms[:n.value]
+
+    def unpack_to_device(self, blob, cols, stream=None):
+        """cc_unpack_to_device: decode a packed host blob into device column tensors ({name: tensor}, n rows each)."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        s = abi.cc_batch_out()
+        for name, _ in abi.BATCH_COLUMNS:
+            t = cols.get(name)
+            setattr(s, name, t.data_ptr() if t is not None else None)
+        _check(self.L.cc_unpack_to_device(self.h, blob.ctypes.data, blob.nbytes, C.byref(s), _stream_ptr(stream)))
+
     def sync(self):
         _check(self.L.cc_sync(self.h))
 
@@ -519,6 +575,15 @@ class Engine:
                                 np.zeros(m, np.uint8), np.zeros(m, np.uint64), np.zeros(m, np.uint64))
         _check(self.L.cc_read_map_table(self.h, m, C.byref(n), _np(sl), _np(kt), _np(k), _np(vt), _np(v), _np(ci)))
         return sl, kt, k, vt, v, ci
+
+
+def host_register(arr):
+    """Page-lock a numpy array's memory (cc_host_register) so asynchronous copies from / into it overlap."""
+    _check(lib().cc_host_register(C.c_void_p(arr.ctypes.data), arr.nbytes))
+
+
+def host_unregister(arr):
+    _check(lib().cc_host_unregister(C.c_void_p(arr.ctypes.data)))
 
 
 def quorum_commit(match, term_start, commit_in, commit_out, stream=None):

@@ -587,6 +587,118 @@ int  cc_split_batch(const cc_batch* in, uint64_t n, const uint8_t* rank_of_inst,
 int  cc_merge_results(const uint32_t* inst, uint64_t n, const uint8_t* rank_of_inst, uint32_t n_inst, uint32_t world,
                       uint32_t threads, const cc_results* parts, const cc_results* out);
 
+/* ---- packed host batches (copycat_amd/csrc/pack.cpp, unpack.hip, host_path.hip) ---------------------------------------
+ * The host-memory calls above ship index / key / a / b / aux as full u64 and inst as u32: 30 B per commit for the six
+ * columns of a value batch, and the H2D of those bytes is most of a PCIe-inclusive step.  In a committed log a run of
+ * consecutive rows has indices, instance slots and operands close to each other, so a batch packs exactly into a
+ * per-block base plus narrow offsets; a gfx950 kernel (k_unpack) widens it back into the ordinary columns in HBM.
+ *
+ * One contiguous, 16-byte-aligned host blob per batch:  header | directory | data
+ *   header     cc_pack_header (64 B)
+ *   directory  cc_pack_block[blocks] (160 B each), block k = rows [4096 k, min(n, 4096 (k + 1)))
+ *   data       per block one data area; per present column its packed rows at `offset` inside the area
+ * Every offset is a multiple of 16; block areas lie after the directory, ascending and non-overlapping; a column's
+ * packed rows (rows * width bytes, rounded up to 16) lie inside its block's area and overlap no other column's.
+ * `present` bit c is column c in cc_batch order (index, time, inst, op, flags, key, a, b, aux); a column is present in
+ * every block or in none (the NULL column pointer of cc_batch).  Entries of absent columns are ignored (written 0).
+ *
+ *   mode         value of a row                                              widths (bytes)
+ *   CC_PK_FOR    base + zero_extend(offset), modulo the column's native      0, 1, 2, 4, 8, never above the native
+ *                width (64 bits; inst 32; op and flags 8)                    width; 0: every row equals base; the
+ *                                                                            native width is written with base 0 (raw)
+ *   CC_PK_REL_A  a[row] + sign_extend(offset) modulo 2^64; column b only,    1, 2, 4
+ *                and only with a present
+ * Offsets are little-endian.  The encoder picks, per block and column, the narrowest exact encoding among FOR with
+ * base = the unsigned minimum, FOR with base = the signed minimum (64-bit columns) and REL_A (b); ties go to FOR, then
+ * to the unsigned base.  Decoding reproduces the caller's columns byte for byte, rows an op does not use included:
+ * the format is exact for every input and has no escape path. */
+#define CC_PACK_BLOCK_ROWS 4096
+#define CC_PACK_VERSION    1
+#define CC_PACK_MAGIC      1263551299  /* "CCPK" little-endian */
+#define CC_PACK_COLUMNS    9
+#define CC_PK_FOR          0
+#define CC_PK_REL_A        1
+
+typedef struct cc_pack_header {
+  uint32_t magic;       /* CC_PACK_MAGIC */
+  uint32_t version;     /* CC_PACK_VERSION */
+  uint64_t n;           /* rows */
+  uint64_t blocks;      /* ceil(n / CC_PACK_BLOCK_ROWS) */
+  uint64_t bytes;       /* the whole blob */
+  uint32_t present;     /* 9-bit column mask */
+  uint32_t block_rows;  /* CC_PACK_BLOCK_ROWS */
+  uint64_t reserved[3];
+} cc_pack_header;
+
+typedef struct cc_pack_col {
+  uint8_t  mode;        /* CC_PK_* */
+  uint8_t  width;       /* bytes per row */
+  uint16_t reserved16;
+  uint32_t offset;      /* of the column's packed rows inside the block's data area */
+  uint64_t base;
+} cc_pack_col;
+
+typedef struct cc_pack_block {
+  uint32_t rows;        /* CC_PACK_BLOCK_ROWS, or the tail's */
+  uint32_t bytes;       /* length of the block's data area */
+  uint64_t offset;      /* of the block's data area from the blob start */
+  cc_pack_col col[9];
+} cc_pack_block;
+
+/* Host side, no GPU involved.  cc_pack_bound: the worst-case blob size of n rows with the `present` columns.
+ * cc_pack_batch: h_cols (NULL column = absent) -> h_blob (16-byte aligned, cap bytes); *bytes = the blob's size; a cap
+ * too small returns CC_ERR_CAPACITY with *bytes = the size needed and writes nothing.  One block at a time per thread
+ * (the block stays in cache between the min / max pass and the narrow write); threads = 0: hardware concurrency.
+ * cc_pack_check: the single validator every consumer runs first: magic, version, sizes, the directory inside the blob,
+ * every block's rows (their sum = n), every offset aligned, inside its area and non-overlapping, mode and width legal
+ * for the column, REL_A only on b and only with a.  Any violation is CC_ERR_INVALID (message: cc_last_error); a blob
+ * that passes decodes without a read outside `bytes` or a write outside n output rows.  *n / *present (optional).
+ * cc_unpack_batch: the host decoder (h_out: every present column non-NULL, n rows). */
+int  cc_pack_bound(uint64_t n, uint32_t present, uint64_t* bytes);
+int  cc_pack_batch(const cc_batch* h_cols, uint64_t n, void* h_blob, uint64_t cap, uint32_t threads, uint64_t* bytes);
+int  cc_pack_check(const void* h_blob, uint64_t bytes, uint64_t* n, uint32_t* present);
+int  cc_unpack_batch(const void* h_blob, uint64_t bytes, const cc_batch_out* h_out, uint32_t threads);
+
+/* Copy a packed host blob to the device and decode it into the caller's device columns (n rows each, present columns
+ * non-NULL, 16-byte aligned); stream-ordered on `stream` (the blob is copied into an engine-owned buffer that the next
+ * call on this engine reuses: sync before the host blob or that engine is used again).  For hosts that keep columns
+ * resident (cc_apply_batch, cc_apply_batch_prefix) but receive them over PCIe.  cc_pack_check runs first: a malformed
+ * blob never reaches the GPU. */
+int  cc_unpack_to_device(cc_engine* e, const void* h_blob, uint64_t bytes, const cc_batch_out* d_cols, void* stream);
+
+typedef struct cc_packed_opts {
+  uint64_t chunk_rows;  /* rows per pipeline chunk; 0 = 16 Mi; rounded up to whole blocks, capped by max_batch and the
+                           engine's extended sub-batch */
+  uint32_t flags;       /* CC_PACKED_* */
+  uint32_t reserved32;
+  uint64_t reserved[2];
+} cc_packed_opts;
+#define CC_PACKED_TIMELINE 1  /* record HIP events around every chunk's stages (cc_packed_timeline) */
+/* cc_apply_batch_host_events on a packed blob (h_events may be NULL: then as cc_apply_batch_host; opts may be NULL),
+ * pipelined inside the library: the batch goes in chunks of whole blocks, and while chunk k is decoded and applied on
+ * the engine's stream, chunk k+1's bytes travel H2D on a copy-in stream and chunk k-1's results travel D2H on a
+ * copy-out stream, straight into h_out rows [lo, hi).  Page-lock h_blob and h_out (cc_host_register) or the copies
+ * do not overlap.  Results, events (pos = batch rows), state and applied index are those of one
+ * cc_apply_batch_host_events call on the decoded columns.
+ * Failure: that of consecutive cc_apply_batch_host_events calls over the chunks.  The call stops at the first failing
+ * chunk and returns its code; *h_rows_done (may be NULL) = the rows of the chunks fully applied (n on success);
+ * *h_events->count = the events of those chunks plus the failing chunk's count; result rows of chunks not applied
+ * keep what the caller had.  With an event stream or on an engine with maps each chunk runs under a device checkpoint
+ * (as the parts of cc_apply_batch_host_prefix do), and a chunk that fails on a full event stream or map table region
+ * is rolled back: the state is then exactly the one after *h_rows_done rows, where the host resumes.  A malformed
+ * blob is CC_ERR_INVALID before anything is copied or launched.  n == 0: CC_OK, no launch, *h_events->count = 0. */
+int  cc_apply_batch_host_packed(cc_engine* e, const void* h_blob, uint64_t bytes, const cc_results* h_out,
+                                const cc_events* h_events, const cc_packed_opts* opts, uint64_t* h_rows_done);
+
+/* The stage times of the last cc_apply_batch_host_packed call made with CC_PACKED_TIMELINE, from HIP events: *chunks =
+ * the chunks that completed; h_ms (4 floats per chunk, room for cap chunks) = H2D, decode, apply, D2H milliseconds. */
+int  cc_packed_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms);
+
+/* hipHostRegister / hipHostUnregister: page-lock caller memory (a packed blob, result columns, an off-heap segment) so
+ * the asynchronous copies of the host calls overlap with the kernels.  NULL or zero bytes: CC_ERR_INVALID. */
+int  cc_host_register(void* h_ptr, uint64_t bytes);
+int  cc_host_unregister(void* h_ptr);
+
 #ifdef __cplusplus
 }
 #endif
