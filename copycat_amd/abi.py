@@ -279,6 +279,17 @@ class cc_pack_block(C.Structure):
     _fields_ = [("rows", C.c_uint32), ("bytes", C.c_uint32), ("offset", C.c_uint64), ("col", cc_pack_col * 9)]
 
 
+# packed result blobs (include/copycat_apply.h "packed result blobs"; copycat_amd/csrc/respack.cpp, respack.hip)
+CC_RESPACK_MAGIC = 1380991811
+CC_RESPACK_VERSION = 1
+CC_RESPACK_COLUMNS = 2
+RESULT_COLUMNS = ("status", "value")  # cc_respack_block.col order
+
+
+class cc_respack_block(C.Structure):
+    _fields_ = [("rows", C.c_uint32), ("bytes", C.c_uint32), ("offset", C.c_uint64), ("col", cc_pack_col * 2)]
+
+
 class cc_packed_opts(C.Structure):
     _fields_ = [
         ("chunk_rows", C.c_uint64),

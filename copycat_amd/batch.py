@@ -150,6 +150,86 @@ def pack_info(blob):
             "bytes_per_row": hd.bytes / n if n else 0.0, "columns": cols}
 
 
+def results_bound(n):
+    """cc_respack_bound: the worst-case size of a packed result blob of n rows."""
+    import ctypes as C
+
+    bound = C.c_uint64()
+    rc = _pack_lib().cc_respack_bound(n, C.byref(bound))
+    if rc:
+        _pack_fail(rc)
+    return bound.value
+
+
+def pack_results(status, value, threads=0, out=None):
+    """cc_respack_pack, the host reference encoder: result rows (status uint8, value uint64) as one packed result blob,
+    a 16-byte-aligned uint8 array.  `out`: a 16-byte-aligned uint8 buffer to pack into; the result is a view of it."""
+    import ctypes as C
+
+    status = np.ascontiguousarray(status, dtype=np.uint8)
+    value = np.ascontiguousarray(value)
+    value = value.view(np.uint64) if value.dtype == np.int64 else np.ascontiguousarray(value, dtype=np.uint64)
+    if len(status) != len(value):
+        raise ValueError(f"status has {len(status)} rows, value {len(value)}")
+    n = len(status)
+    blob = out if out is not None else _aligned_bytes(results_bound(n))
+    r = abi.cc_results(status.ctypes.data, value.ctypes.data)
+    size = C.c_uint64()
+    rc = _pack_lib().cc_respack_pack(C.byref(r), n, blob.ctypes.data, blob.nbytes, threads, C.byref(size))
+    if rc:
+        _pack_fail(rc)
+    return blob[:size.value]
+
+
+def results_check(blob):
+    """cc_respack_check: the rows of a well-formed result blob; raises EngineError (CC_ERR_INVALID) otherwise."""
+    import ctypes as C
+
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    n = C.c_uint64()
+    rc = _pack_lib().cc_respack_check(blob.ctypes.data, blob.nbytes, C.byref(n))
+    if rc:
+        _pack_fail(rc)
+    return n.value
+
+
+def unpack_results(blob, threads=0):
+    """cc_respack_unpack, the host decoder: (status, value) numpy columns of a packed result blob."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    n = results_check(blob)
+    status, value = np.zeros(n, np.uint8), np.zeros(n, np.uint64)
+    r = abi.cc_results(status.ctypes.data, value.ctypes.data)
+    import ctypes as C
+
+    rc = _pack_lib().cc_respack_unpack(blob.ctypes.data, blob.nbytes, C.byref(r), threads)
+    if rc:
+        _pack_fail(rc)
+    return status, value
+
+
+def results_info(blob):
+    """The directory of a packed result blob, as pack_info: {"n", "blocks", "bytes", "bytes_per_row", "columns":
+    {"status" / "value": {"rows": {(mode, width): rows}, "bytes_per_row", "blocks": [(mode, width, base), ...]}}}."""
+    import ctypes as C
+
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    n = results_check(blob)
+    hd = abi.cc_pack_header.from_buffer_copy(blob[:C.sizeof(abi.cc_pack_header)].tobytes())
+    lo = C.sizeof(abi.cc_pack_header)
+    dir_ = (abi.cc_respack_block * hd.blocks).from_buffer_copy(
+        blob[lo:lo + hd.blocks * C.sizeof(abi.cc_respack_block)].tobytes())
+    cols = {}
+    for c, name in enumerate(abi.RESULT_COLUMNS):
+        rows, blocks, size = {}, [], 0
+        for blk in dir_:
+            e = blk.col[c]
+            rows[(e.mode, e.width)] = rows.get((e.mode, e.width), 0) + blk.rows
+            blocks.append((e.mode, e.width, e.base))
+            size += blk.rows * e.width
+        cols[name] = {"rows": rows, "blocks": blocks, "bytes_per_row": size / n if n else 0.0}
+    return {"n": n, "blocks": hd.blocks, "bytes": hd.bytes, "bytes_per_row": hd.bytes / n if n else 0.0, "columns": cols}
+
+
 def tagged(v):
     """Python value -> canonical (tag, payload).  None -> NULL; bool -> BOOL; int -> LONG.
 

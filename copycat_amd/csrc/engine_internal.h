@@ -738,4 +738,19 @@ struct UnpackArgs {
 int launch_unpack(const UnpackArgs& a, uint32_t blocks, hipStream_t st);
 int pack_err(int code, const char* what);  // pack.cpp's route to cc_last_error
 
+// Wide result columns -> the directory and data areas of a result blob (respack.hip): block k of `dir` encodes rows
+// [4096 k, ...) of status / value (both 16-byte aligned).  `data` takes the blob's bytes from blob offset `data_base`
+// (a multiple of 16) on, with room for the worst case (9 bytes per row + 32); *total = the data bytes written.
+struct RespackArgs {
+  const uint8_t* status;
+  const uint64_t* value;
+  uint64_t n;
+  cc_respack_block* dir;
+  uint8_t* data;
+  uint64_t data_base;
+  unsigned long long* total;
+};
+constexpr uint32_t kRespackPlacePass = 256;  // blocks one pass of the placement scan holds (one per lane)
+int launch_respack(const RespackArgs& a, hipStream_t st);
+
 }  // namespace cc

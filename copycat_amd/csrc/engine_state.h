@@ -414,6 +414,11 @@ struct cc_engine {
   hipEvent_t pk_landed[2] = {}, pk_drained[2] = {};
   std::vector<hipEvent_t> pk_stamp;  // 8 per chunk of the last call: H2D, decode, apply, D2H begin / end
   uint64_t pk_chunks = 0;            // chunks of the last call whose stamps are all recorded
+  // cc_apply_batch_host_packed_results shares the streams and the landed / drained events; its own stamps, and the
+  // pinned host word the encoder's data-byte total is read back into (also cc_respack_from_device's)
+  std::vector<hipEvent_t> rp_stamp;  // 10 per chunk of the last call: H2D, decode, apply, encode, D2H begin / end
+  uint64_t rp_chunks = 0;
+  uint64_t* rp_pin = nullptr;
   // per-kernel profiling (cc_profile_enable)
   bool prof_on = false;
   std::vector<hipEvent_t> ev_pool;

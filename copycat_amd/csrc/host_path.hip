@@ -945,6 +945,289 @@ extern "C" int cc_packed_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, 
   return CC_OK;
 }
 
+// ---- packed result blobs (respack.cpp, respack.hip) -------------------------------------------------------------------
+// cc_apply_batch_host_packed_results is cc_apply_batch_host_packed with a fourth stage on the engine's stream:
+//
+//   copy-in  (pk_in)      | H2D 0 | H2D 1 |      H2D 2      |
+//   engine   (own_stream)         | dec 0 + apply 0 + enc 0 | dec 1 + apply 1 + enc 1 | ...
+//   copy-out (pk_out)                                       | D2H 0 |                 | D2H 1 |
+//
+// The encoder (three launches, respack.hip) turns the chunk's wide result rows into directory entries and data areas
+// in one of two device stagings: {total word (16 B) | the chunk's directory entries | its data areas}.  Chunk k's areas
+// are placed from the blob offset where chunk k - 1's ended, which the host knows after chunk k - 1's cc_sync: the
+// encoder's total is copied into a pinned host word on the engine's stream before that sync, so it costs no round trip
+// of its own.  The copy-out then sends the directory entries and the data bytes used, and only those, to their places
+// in the caller's blob; the wide rows never leave HBM, so one wide result set is enough.  The body below follows
+// cc_apply_batch_host_packed stage by stage; that call is left as it was (it is the baseline this one is measured
+// against).
+namespace {
+
+enum RpSlot : int { kHwRes0 = kPkSlots, kHwRes1, kRpSlots };
+static_assert(kRpSlots <= 32, "cc_engine::hw_buf");
+constexpr uint64_t kRpHead = 16;  // the staging's first bytes: the encoder's total word
+
+uint64_t rp_blocks(uint64_t n) { return (n + CC_PACK_BLOCK_ROWS - 1) / CC_PACK_BLOCK_ROWS; }
+
+// rows [0, m) of d_status / d_value encoded into staging `slot` on `st`, the data areas placed from blob offset
+// `data_base` on; the total then travels into the pinned word on `st` too.  *stage = the staging.
+int rp_encode(cc_engine* e, int slot, const void* d_status, const void* d_value, uint64_t m, uint64_t data_base,
+              hipStream_t st, uint8_t** stage) {
+  if (!e->rp_pin) HIPCHECK(hipHostMalloc((void**)&e->rp_pin, 16, hipHostMallocDefault));
+  const uint64_t db = rp_blocks(m) * sizeof(cc_respack_block);
+  void* p = nullptr;
+  TRY(hw(e, slot, kRpHead + db + 9 * m + 32, &p));  // (every column raw; the tail block's two paddings)
+  RespackArgs a{};
+  a.status = (const uint8_t*)d_status, a.value = (const uint64_t*)d_value, a.n = m;
+  a.dir = (cc_respack_block*)((uint8_t*)p + kRpHead);
+  a.data = (uint8_t*)p + kRpHead + db;
+  a.data_base = data_base;
+  a.total = (unsigned long long*)p;
+  if (launch_respack(a, st)) return set_err(CC_ERR_HIP, "result blob encode launch", hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(e->rp_pin, p, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  *stage = (uint8_t*)p;
+  return CC_OK;
+}
+
+void rp_header(void* h_blob, uint64_t n, uint64_t bytes) {
+  cc_pack_header hd{};
+  hd.magic = (uint32_t)CC_RESPACK_MAGIC;
+  hd.version = CC_RESPACK_VERSION;
+  hd.n = n;
+  hd.blocks = rp_blocks(n);
+  hd.bytes = bytes;
+  hd.present = 3;
+  hd.block_rows = CC_PACK_BLOCK_ROWS;
+  std::memcpy(h_blob, &hd, sizeof hd);
+}
+
+}  // namespace
+
+extern "C" int cc_respack_from_device(cc_engine* e, const cc_results* d_results, uint64_t n, void* h_blob, uint64_t cap,
+                                      uint64_t* bytes, void* stream) {
+  if (!e || !d_results || !bytes || !h_blob) return set_err(CC_ERR_INVALID, "result blob: null argument");
+  if ((uintptr_t)h_blob & 15) return set_err(CC_ERR_INVALID, "result blob: the blob must be 16-byte aligned");
+  uint64_t bound = 0;
+  TRY(cc_respack_bound(n, &bound));
+  if (cap < bound) {
+    *bytes = bound;
+    return set_err(CC_ERR_CAPACITY, "result blob: the blob buffer is smaller than cc_respack_bound (*bytes = the bound)");
+  }
+  if (n == 0) {
+    rp_header(h_blob, 0, sizeof(cc_pack_header));
+    *bytes = sizeof(cc_pack_header);
+    return CC_OK;
+  }
+  if (!d_results->status || !d_results->value || (((uintptr_t)d_results->status | (uintptr_t)d_results->value) & 15))
+    return set_err(CC_ERR_INVALID, "result blob: status and value device pointers must be non-null and 16-byte aligned");
+  if (rp_blocks(n) > 0x7FFFFFFFull) return set_err(CC_ERR_CAPACITY, "result blob: more than 2^31 blocks");
+  HIPCHECK(hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t db = rp_blocks(n) * sizeof(cc_respack_block);
+  uint8_t* stage = nullptr;
+  TRY(rp_encode(e, kHwRes0, d_results->status, d_results->value, n, sizeof(cc_pack_header) + db, st, &stage));
+  HIPCHECK(hipStreamSynchronize(st));
+  const uint64_t total = *e->rp_pin;
+  if (total > 9 * n + 32) return set_err(CC_ERR_STATE, "internal check: the result blob encoder wrote past its bound");
+  // directory and data are adjacent in the staging as they are in the blob: one copy
+  HIPCHECK(hipMemcpyAsync((uint8_t*)h_blob + sizeof(cc_pack_header), stage + kRpHead, db + total, hipMemcpyDeviceToHost, st));
+  HIPCHECK(hipStreamSynchronize(st));
+  *bytes = sizeof(cc_pack_header) + db + total;
+  rp_header(h_blob, n, *bytes);
+  return CC_OK;
+}
+
+extern "C" int cc_apply_batch_host_packed_results(cc_engine* e, const void* h_blob, uint64_t bytes, void* h_res_blob,
+                                                  uint64_t res_cap, uint64_t* res_bytes, const cc_events* hev,
+                                                  const cc_packed_opts* opts, uint64_t* h_rows_done) {
+  if (h_rows_done) *h_rows_done = 0;
+  if (!e || !h_res_blob || !res_bytes) return set_err(CC_ERR_INVALID, "result blob: null argument");
+  if ((uintptr_t)h_res_blob & 15) return set_err(CC_ERR_INVALID, "result blob: the blob must be 16-byte aligned");
+  if (opts && (opts->flags & ~(uint32_t)CC_PACKED_TIMELINE)) return set_err(CC_ERR_INVALID, "packed apply: unknown flag");
+  uint64_t n = 0;
+  uint32_t present = 0;
+  TRY(cc_pack_check(h_blob, bytes, &n, &present));  // (before anything is copied or launched)
+  TRY(host_events_ok(hev));
+  uint64_t bound = 0;
+  TRY(cc_respack_bound(n, &bound));
+  if (res_cap < bound) {
+    *res_bytes = bound;
+    return set_err(CC_ERR_CAPACITY, "result blob: the blob buffer is smaller than cc_respack_bound (*res_bytes = the bound)");
+  }
+  if (n && (present & kPkNeed) != kPkNeed)
+    return set_err(CC_ERR_INVALID, "inst/op/flags/a/b columns and status/value outputs are required");
+  // from here on every return leaves a valid blob of the rows copied out so far
+  rp_header(h_res_blob, 0, sizeof(cc_pack_header));
+  *res_bytes = sizeof(cc_pack_header);
+  HIPCHECK(hipSetDevice(e->device));
+  e->rp_chunks = 0;
+  if (n == 0) {
+    if (hev) *hev->count = 0;
+    return CC_OK;
+  }
+  e->last_err_bits = 0;
+  hipStream_t st = e->own_stream;
+  if (st != e->last_stream) HIPCHECK(hipStreamSynchronize(e->last_stream));
+  e->last_stream = st;
+  TRY(pk_init(e));
+
+  const uint64_t kB = CC_PACK_BLOCK_ROWS;
+  uint64_t chunk = opts && opts->chunk_rows ? opts->chunk_rows : (16ull << 20);
+  chunk = std::min<uint64_t>(chunk, 1ull << 40);
+  chunk = (chunk + kB - 1) / kB * kB;
+  const uint64_t cap_rows = std::max<uint64_t>(std::min(e->cfg.max_batch, e->sub_ext) / kB * kB, kB);
+  chunk = std::min(chunk, cap_rows);
+  const uint64_t bpc = chunk / kB, nchunks = (n + chunk - 1) / chunk;
+  const bool ck = e->map_bits != 0 || hev != nullptr;  // as the parts of cc_apply_batch_host_prefix
+  if (ck) TRY(ckpt_reserve(e));
+  const bool stamps = opts && (opts->flags & CC_PACKED_TIMELINE);
+  if (stamps)
+    while (e->rp_stamp.size() < 10 * nchunks) {
+      hipEvent_t ev;
+      HIPCHECK(hipEventCreate(&ev));
+      e->rp_stamp.push_back(ev);
+    }
+  auto stamp = [&](uint64_t k, int which, hipStream_t s) -> hipError_t {
+    return stamps ? hipEventRecord(e->rp_stamp[10 * k + which], s) : hipSuccess;
+  };
+
+  const cc_pack_header* hd = (const cc_pack_header*)h_blob;
+  const uint8_t* const blob = (const uint8_t*)h_blob;
+  const cc_pack_block* const dir = (const cc_pack_block*)(blob + sizeof *hd);
+  void* piece[2] = {};
+  uint64_t piece_base[2] = {}, piece_dir[2] = {};
+  // chunk k's piece on its way: directory entries, then the data areas of its blocks
+  auto send = [&](uint64_t k) -> int {
+    const uint64_t b0 = k * bpc, b1 = std::min(hd->blocks, b0 + bpc);
+    const uint64_t lo = dir[b0].offset, hi = dir[b1 - 1].offset + dir[b1 - 1].bytes, db = (b1 - b0) * sizeof(cc_pack_block);
+    void* p = nullptr;
+    TRY(hw(e, kHwBlob0 + (int)(k & 1), db + (hi - lo), &p));
+    HIPCHECK(stamp(k, 0, e->pk_in));
+    HIPCHECK(hipMemcpyAsync(p, dir + b0, db, hipMemcpyHostToDevice, e->pk_in));
+    if (hi > lo) HIPCHECK(hipMemcpyAsync((uint8_t*)p + db, blob + lo, hi - lo, hipMemcpyHostToDevice, e->pk_in));
+    HIPCHECK(stamp(k, 1, e->pk_in));
+    HIPCHECK(hipEventRecord(e->pk_landed[k & 1], e->pk_in));
+    piece[k & 1] = p, piece_base[k & 1] = lo, piece_dir[k & 1] = db;
+    return CC_OK;
+  };
+  uint8_t* const res = (uint8_t*)h_res_blob;
+  // the result blob keeps the room of all n rows' directory entries; the data areas follow, chunk after chunk
+  const uint64_t res_data0 = sizeof(cc_pack_header) + rp_blocks(n) * sizeof(cc_respack_block);
+  uint64_t res_rows = 0, res_data = 0;  // rows whose results are on their way out, and their data bytes
+  uint64_t ev_n = 0;                    // events of the chunks so far (the failing chunk's included)
+  // every stream drained before the call returns: a copy in flight reads the caller's blob or writes its result blob;
+  // the host writes the header last
+  auto leave = [&](int rc) {
+    (void)hipStreamSynchronize(e->pk_in);
+    (void)hipStreamSynchronize(e->pk_out);
+    if (hev) *hev->count = ev_n;
+    *res_bytes = res_rows ? res_data0 + res_data : sizeof(cc_pack_header);
+    rp_header(res, res_rows, *res_bytes);
+    return rc;
+  };
+  int rc = send(0);
+  if (rc) return leave(rc);
+  for (uint64_t k = 0; k < nchunks; ++k) {
+    const uint64_t lo = k * chunk, hi = std::min(n, lo + chunk), m = hi - lo;
+    const int s = (int)(k & 1);
+    if (k + 1 < nchunks && (rc = send(k + 1))) return leave(rc);
+    // decode: the wide columns of rows [lo, hi)
+    void* dcol[9] = {};
+    for (int c = 0; c < 9; ++c)
+      if (((present >> c) & 1) && (rc = hw(e, kHwCol + c, kPkEsz[c] * m, &dcol[c]))) return leave(rc);
+    void *d_status, *d_value;
+    if ((rc = hw(e, kHwStatus, m, &d_status)) || (rc = hw(e, kHwValue, 8 * m, &d_value))) return leave(rc);
+    hipError_t x = hipStreamWaitEvent(st, e->pk_landed[s], 0);
+    if (x == hipSuccess) x = stamp(k, 2, st);
+    if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: wait for the piece", x));
+    if (launch_unpack(unpack_args(piece[s], (const uint8_t*)piece[s] + piece_dir[s], piece_base[s], dcol, present),
+                      (uint32_t)((m + kB - 1) / kB), st))
+      return leave(set_err(CC_ERR_HIP, "unpack launch", hipGetLastError()));
+    x = stamp(k, 3, st);
+    // the wide rows stay in HBM (sentinels as in apply_host); chunk k - 1's encode has read them on this stream
+    if (x == hipSuccess) x = hipMemsetAsync(d_status, 0xFF, m, st);
+    if (x == hipSuccess) x = hipMemsetAsync(d_value, 0xA5, 8 * m, st);
+    if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: result prefill", x));
+    // the chunk's events are appended to the host stream from the events so far on
+    uint64_t cnt = 0;
+    cc_events v{}, dev{};
+    if (hev) {
+      v = *hev;
+      const uint64_t used = std::min(ev_n, hev->capacity);
+      v.pos += used, v.target += used, v.code += used, v.src += used, v.tag += used, v.payload += used;
+      v.capacity -= used;
+      v.count = &cnt;
+    }
+    if ((rc = hw_events(e, hev ? &v : nullptr, &dev))) return leave(rc);
+    if (ck && (rc = ckpt_save(e))) return leave(rc);
+    const cc_batch d{(const uint64_t*)dcol[0], (const uint64_t*)dcol[1], (const uint32_t*)dcol[2],
+                     (const uint8_t*)dcol[3],  (const uint8_t*)dcol[4],  (const uint64_t*)dcol[5],
+                     (const uint64_t*)dcol[6], (const uint64_t*)dcol[7], (const uint64_t*)dcol[8]};
+    const cc_results r{(uint8_t*)d_status, (uint64_t*)d_value};
+    (void)stamp(k, 4, st);
+    e->last_err_bits = 0;
+    rc = cc_apply_batch(e, &d, m, &r, hev ? &dev : nullptr, st);
+    if (rc) {
+      (void)hipStreamSynchronize(st);
+      return leave(rc);
+    }
+    (void)stamp(k, 5, st);
+    // encode into staging s once its copy-out of chunk k - 2 is done; the total comes back with the chunk's checks
+    uint8_t* stage = nullptr;
+    if (k >= 2 && (x = hipStreamWaitEvent(st, e->pk_drained[s], 0)) != hipSuccess)
+      return leave(set_err(CC_ERR_HIP, "packed apply: wait for the result staging", x));
+    (void)stamp(k, 6, st);
+    if ((rc = rp_encode(e, kHwRes0 + s, d_status, d_value, m, res_data0 + res_data, st, &stage))) {
+      (void)hipStreamSynchronize(st);
+      return leave(rc);
+    }
+    (void)stamp(k, 7, st);
+    const int rs = cc_sync(e);  // device-side checks (capacity, unsupported ops, time order); the stream is drained
+    const int re = hw_events_back(e, hev ? &v : nullptr, &dev);
+    for (uint64_t i = 0; hev && lo && i < std::min(cnt, v.capacity); ++i) v.pos[i] += (uint32_t)lo;
+    ev_n += cnt;
+    rc = rs ? rs : re;
+    bool rolled_back = false;
+    if (rc == CC_ERR_CAPACITY && ck) {  // a full event stream or map table region, and nothing else: not applied
+      const uint32_t bits = e->last_err_bits;
+      if (bits && !(bits & ~(kErrCapacity | kErrEvents))) {
+        const int rr = ckpt_restore(e);
+        if (rr) return leave(rr);
+        e->last_err_bits = bits;
+        rolled_back = true;
+      }
+    }
+    if (!rolled_back) {  // (a failing chunk that stays applied returns its rows, as cc_apply_batch_host does)
+      const uint64_t total = *e->rp_pin, db = rp_blocks(m) * sizeof(cc_respack_block);
+      if (total > 9 * m + 32)
+        return leave(set_err(CC_ERR_STATE, "internal check: the result blob encoder wrote past its bound"));
+      x = stamp(k, 8, e->pk_out);
+      if (x == hipSuccess)
+        x = hipMemcpyAsync(res + sizeof(cc_pack_header) + (lo / kB) * sizeof(cc_respack_block), stage + kRpHead, db,
+                           hipMemcpyDeviceToHost, e->pk_out);
+      if (x == hipSuccess && total)
+        x = hipMemcpyAsync(res + res_data0 + res_data, stage + kRpHead + db, total, hipMemcpyDeviceToHost, e->pk_out);
+      if (x == hipSuccess) x = stamp(k, 9, e->pk_out);
+      if (x == hipSuccess) x = hipEventRecord(e->pk_drained[s], e->pk_out);
+      if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: result blob copy-out", x));
+      res_rows = hi, res_data += total;
+    }
+    if (rc) return leave(rc);
+    if (h_rows_done) *h_rows_done = hi;
+    e->rp_chunks = stamps ? k + 1 : 0;
+  }
+  return leave(CC_OK);
+}
+
+extern "C" int cc_packed_results_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms) {
+  if (!e || !chunks || (cap && !h_ms)) return set_err(CC_ERR_INVALID, "null argument");
+  HIPCHECK(hipSetDevice(e->device));
+  *chunks = e->rp_chunks;
+  for (uint64_t k = 0; k < std::min(cap, e->rp_chunks); ++k)
+    for (int j = 0; j < 5; ++j)
+      HIPCHECK(hipEventElapsedTime(h_ms + 5 * k + j, e->rp_stamp[10 * k + 2 * j], e->rp_stamp[10 * k + 2 * j + 1]));
+  return CC_OK;
+}
+
 extern "C" int cc_sessions_close_host(cc_engine* e, const uint64_t* h_clients, uint64_t count, const cc_events* h_events,
                                       uint64_t* h_closed) {
   if (!e) return set_err(CC_ERR_INVALID, "null engine");

@@ -117,6 +117,13 @@ def lib():
             "cc_packed_timeline": (i32, [P, u64, P, P]),
             "cc_host_register": (i32, [P, u64]),
             "cc_host_unregister": (i32, [P]),
+            "cc_respack_bound": (i32, [u64, P]),
+            "cc_respack_pack": (i32, [P, u64, P, u64, u32, P]),
+            "cc_respack_check": (i32, [P, u64, P]),
+            "cc_respack_unpack": (i32, [P, u64, P, u32]),
+            "cc_respack_from_device": (i32, [P, P, u64, P, u64, P, P]),
+            "cc_apply_batch_host_packed_results": (i32, [P, P, u64, P, u64, P, P, P, P]),
+            "cc_packed_results_timeline": (i32, [P, u64, P, P]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -432,6 +439,58 @@ class Engine:
         _check(self.L.cc_packed_timeline(self.h, 0, C.byref(n), None))
         ms = np.zeros((max(n.value, 1), 4), np.float32)
         _check(self.L.cc_packed_timeline(self.h, n.value, C.byref(n), _np(ms)))
+        return ms[:n.value]
+
+    def results_to_host_packed(self, status, value, stream=None, out=None):
+        """cc_respack_from_device: device result tensors (status uint8, value 64-bit, n rows each, 16-byte aligned) ->
+        a packed result blob in host memory (batch.unpack_results decodes it), byte for byte batch.pack_results of the
+        same rows.  Synchronous.  `out`: a 16-byte-aligned uint8 buffer of at least batch.results_bound(n) bytes."""
+        from .batch import _aligned_bytes, results_bound
+
+        n = status.numel()
+        blob = out if out is not None else _aligned_bytes(results_bound(n))
+        r = abi.cc_results(status.data_ptr(), value.data_ptr())
+        size = C.c_uint64()
+        _check(self.L.cc_respack_from_device(self.h, C.byref(r), n, blob.ctypes.data, blob.nbytes, C.byref(size),
+                                             _stream_ptr(stream)))
+        return blob[:size.value]
+
+    def apply_host_packed_results(self, blob, n, capacity=None, chunk_rows=0, events=True, out=None, timeline=False):
+        """cc_apply_batch_host_packed_results: apply_host_packed with the results as a packed result blob.  Returns
+        (result_blob, events, rows_done); batch.unpack_results(result_blob) gives the (status, value) rows of the chunks
+        whose results the wide call copies out (results_info(result_blob)["n"] of them).  `out`: a 16-byte-aligned uint8
+        buffer of at least batch.results_bound(n) bytes to write the blob into (e.g. page-locked with host_register)."""
+        from .batch import _aligned_bytes, results_bound
+
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        res = out if out is not None else _aligned_bytes(results_bound(n))
+        opts = abi.cc_packed_opts(chunk_rows=chunk_rows, flags=abi.CC_PACKED_TIMELINE if timeline else 0)
+        done, size = C.c_uint64(), C.c_uint64()
+        ev, cols, count = None, None, np.zeros(1, np.uint64)
+        if events:
+            cap = capacity if capacity is not None else max(4 * n, 1024)
+            cols = {"pos": np.zeros(cap, np.uint32), "target": np.zeros(cap, np.uint32), "code": np.zeros(cap, np.uint8),
+                    "src": np.zeros(cap, np.uint8), "tag": np.zeros(cap, np.uint8), "payload": np.zeros(cap, np.uint64)}
+            ev = abi.cc_events(*(cols[k].ctypes.data for k in ("pos", "target", "code", "src", "tag", "payload")), cap,
+                               count.ctypes.data)
+        rc = self.L.cc_apply_batch_host_packed_results(self.h, blob.ctypes.data, blob.nbytes, res.ctypes.data, res.nbytes,
+                                                       C.byref(size), C.byref(ev) if ev is not None else None,
+                                                       C.byref(opts), C.byref(done))
+        if rc != abi.CC_OK and not (rc == abi.CC_ERR_CAPACITY and done.value < n and size.value <= res.nbytes):
+            _check(rc)
+        evs = None
+        if events:
+            m = int(min(count[0], cap))
+            evs = {k: v[:m] for k, v in cols.items()}
+            evs["count"] = int(count[0])
+        return res[:size.value], evs, done.value
+
+    def packed_results_timeline(self):
+        """Per chunk of the last apply_host_packed_results(timeline=True): (H2D, decode, apply, encode, D2H) ms."""
+        n = C.c_uint64()
+        _check(self.L.cc_packed_results_timeline(self.h, 0, C.byref(n), None))
+        ms = np.zeros((max(n.value, 1), 5), np.float32)
+        _check(self.L.cc_packed_results_timeline(self.h, n.value, C.byref(n), _np(ms)))
         return ms[:n.value]
 
     def unpack_to_device(self, blob, cols, stream=None):

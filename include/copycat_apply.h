@@ -699,6 +699,81 @@ int  cc_packed_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_m
 int  cc_host_register(void* h_ptr, uint64_t bytes);
 int  cc_host_unregister(void* h_ptr);
 
+/* ---- packed result blobs (copycat_amd/csrc/respack.cpp, respack.hip, host_path.hip) ----------------------------------
+ * The result-blob calls exist from this commit on, under the unchanged CC_ABI_VERSION 6 (symbols are only added).
+ * The host calls above return results wide: 1 status byte + 8 value bytes per commit.  Within a block of consecutive
+ * rows the values are counters close to each other and the statuses are mostly one byte value, so cc_results packs the
+ * way the operands do.  A gfx950 encoder (respack.hip) writes the blob in HBM and only the narrow bytes travel D2H.
+ *
+ * One contiguous, 16-byte-aligned blob:  header | directory | data
+ *   header     cc_pack_header (64 B): magic CC_RESPACK_MAGIC, version CC_RESPACK_VERSION, present = 3,
+ *              block_rows = CC_PACK_BLOCK_ROWS
+ *   directory  cc_respack_block[blocks] (48 B each), block k = rows [4096 k, min(n, 4096 (k + 1)))
+ *   data       per block one data area; per column its rows at `offset` inside the area (rows * width bytes, rounded
+ *              up to 16, the padding zero)
+ * col[0] is status, col[1] is value.  Every offset is a multiple of 16; block areas lie after the directory, ascending
+ * in block order and non-overlapping; a column's rows lie inside its block's area and overlap no other column's.
+ * The only mode is CC_PK_FOR:
+ *   value    base + zero_extend(offset) modulo 2^64; widths 0, 1, 2, 4, 8; width 8 is the raw column with base 0
+ *   status   widths 0, 1; width 1 is the raw column with base 0; width 0: every row equals base
+ * The encoder takes, per block and column, the narrowest exact width among base = the unsigned minimum and (value)
+ * base = the signed minimum; a tie goes to the unsigned base.  The blob a full encode writes (cc_respack_pack,
+ * cc_respack_from_device, a cc_apply_batch_host_packed_results call that applies every chunk) is a function of the
+ * result columns alone: status area first, value area after it, block areas back to back from the directory's end;
+ * neither the thread count nor the GPU / host split nor the chunking changes a byte.  Decoding reproduces the wide
+ * columns byte for byte, the value bytes of NULL-tagged rows and the 0xFF / 0xA5 prefill of a row no kernel wrote
+ * included; there is no escape path. */
+#define CC_RESPACK_MAGIC   1380991811  /* "CCPR" little-endian */
+#define CC_RESPACK_VERSION 1
+#define CC_RESPACK_COLUMNS 2
+
+typedef struct cc_respack_block {
+  uint32_t rows;        /* CC_PACK_BLOCK_ROWS, or the tail's */
+  uint32_t bytes;       /* length of the block's data area */
+  uint64_t offset;      /* of the block's data area from the blob start */
+  cc_pack_col col[2];   /* status, value */
+} cc_respack_block;
+
+/* Host side, no GPU involved.  cc_respack_bound: the worst-case blob size of n rows.  cc_respack_pack: the reference
+ * encoder, h_results (n rows) -> h_blob (16-byte aligned, cap bytes); *bytes = the blob's size; a cap too small
+ * returns CC_ERR_CAPACITY with *bytes = the size needed and writes nothing.  cc_respack_check: the single validator
+ * (magic, version, present, sizes, the directory inside the blob, every block's rows and their sum, every offset
+ * aligned, inside its area and non-overlapping, mode and width legal for the column); any violation is CC_ERR_INVALID
+ * with a message that names the "result blob"; *n optional.  cc_respack_unpack: the host decoder (validator first;
+ * h_out: n rows each). */
+int  cc_respack_bound(uint64_t n, uint64_t* bytes);
+int  cc_respack_pack(const cc_results* h_results, uint64_t n, void* h_blob, uint64_t cap, uint32_t threads,
+                     uint64_t* bytes);
+int  cc_respack_check(const void* h_blob, uint64_t bytes, uint64_t* n);
+int  cc_respack_unpack(const void* h_blob, uint64_t bytes, const cc_results* h_out, uint32_t threads);
+
+/* Encode device result columns (d_results: status and value in HBM, n rows, both 16-byte aligned) into a result blob
+ * in the caller's host memory: the counterpart of cc_unpack_to_device for hosts that keep columns resident but take
+ * results over PCIe.  The blob is built in engine-owned staging on `stream`; only header + directory + used data bytes
+ * are copied.  Synchronous: on return the stream is drained and the blob is final, byte for byte cc_respack_pack's.
+ * cap < cc_respack_bound(n): CC_ERR_CAPACITY with *bytes = the bound, before any launch.  n == 0: a header-only blob. */
+int  cc_respack_from_device(cc_engine* e, const cc_results* d_results, uint64_t n, void* h_blob, uint64_t cap,
+                            uint64_t* bytes, void* stream);
+
+/* cc_apply_batch_host_packed with the result rows replaced by a result blob: the same chunking, streams, checkpoint /
+ * rollback and event-stream rules; state, events, applied index and *h_rows_done are exactly those of
+ * cc_apply_batch_host_packed on the same input.  Per chunk the encoder runs on the engine's stream after the apply,
+ * and the copy-out stream sends the chunk's directory entries and its data bytes, and only those, into h_res_blob.
+ * On every return after argument validation h_res_blob is a valid result blob (*res_bytes its size) of rows
+ * [0, header.n): the rows whose results the wide call would have copied out, i.e. the applied chunks plus a failing
+ * chunk that stays applied; a rolled-back chunk is excluded (then header.n == *h_rows_done).  Decoded, it equals the
+ * wide call's result rows byte for byte.  When a call stops early the directory keeps the room of all n rows' blocks,
+ * so the data areas start where they do in the full blob.  h_res_blob NULL or not 16-byte aligned: CC_ERR_INVALID;
+ * res_cap < cc_respack_bound(n): CC_ERR_CAPACITY with *res_bytes = the bound, before anything is copied or launched.
+ * opts->flags accepts CC_PACKED_TIMELINE only.  Page-lock both blobs (cc_host_register) or the copies do not overlap. */
+int  cc_apply_batch_host_packed_results(cc_engine* e, const void* h_blob, uint64_t bytes, void* h_res_blob,
+                                        uint64_t res_cap, uint64_t* res_bytes, const cc_events* h_events,
+                                        const cc_packed_opts* opts, uint64_t* h_rows_done);
+
+/* The stage times of the last cc_apply_batch_host_packed_results call made with CC_PACKED_TIMELINE: *chunks = the
+ * chunks that completed; h_ms (5 floats per chunk, room for cap chunks) = H2D, decode, apply, encode, D2H ms. */
+int  cc_packed_results_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
 """The PCIe-inclusive c2 step from host memory: wide columns (cc_apply_batch_host) against a packed blob
-(cc_apply_batch_host_packed).
+(cc_apply_batch_host_packed) against a packed blob in and a packed result blob out (cc_apply_batch_host_packed_results).
 
-Two engines of one build get the same AtomicLongClients steps over 65,536 resources.  The baseline engine takes the six
+Three engines of one build get the same AtomicLongClients steps over 65,536 resources.  The baseline engine takes the six
 wide columns (30 B per commit) from page-locked host memory through cc_apply_batch_host: the same code as before the
 packed path existed, measured in the same run on the same box.  The other engine takes the step packed
 (cc_pack_batch, --threads host threads, timed on its own) through cc_apply_batch_host_packed, blob and result rows
 page-locked.  --warmup untimed steps, then --repeats timed steps per engine, interleaved; host wall clock around the
 synchronous calls; medians with min / max.  Every step's results are compared between the two paths.  Per chunk of
 every timed packed call the H2D, decode, apply and D2H times come from HIP events (CC_PACKED_TIMELINE).  Both paths
-also run once from pageable memory.  Prints one JSON line (and writes it to --out).
+also run once from pageable memory.  The third engine takes the same blob through cc_apply_batch_host_packed_results
+into a page-locked result blob (ms_packed_both; its baseline is ms_packed_call of the same run); the blob is decoded on
+the host (cc_respack_unpack, --threads threads, timed on its own as ms_unpack_results) and compared with the other two
+paths every step; per chunk its H2D, decode, apply, encode and D2H times come from HIP events, and
+encode_over_d2h_saved is the largest encode time over the D2H time the chunk saves against the wide-result call of the
+same step.  Prints one JSON line (and writes it to --out).
 
     python scripts/host_packed_e2e.py [--rows 100000000] [--warmup 2] [--repeats 7] [--threads 16] [--chunk-rows 0]
 """
@@ -27,7 +32,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from copycat_amd import abi  # noqa: E402
-from copycat_amd.batch import Batch, _aligned_bytes, pack, pack_info  # noqa: E402
+from copycat_amd.batch import Batch, _aligned_bytes, pack, pack_info, results_bound, results_check  # noqa: E402
 from copycat_amd.engine import RESULT_SENTINEL, Engine, _check, host_register, host_unregister  # noqa: E402
 from copycat_amd.workload import SEED_C2, AtomicLongClients  # noqa: E402
 
@@ -71,16 +76,19 @@ def main():
     args = ap.parse_args()
     n = args.rows
     clients = AtomicLongClients(resources=R, seed=SEED_C2, threads=args.threads)
-    EW, EP = _engine(n), _engine(n)
+    EW, EP, EB = _engine(n), _engine(n), _engine(n)
     host = Batch(n)
     blob_buf = _aligned_bytes(14 * n + (1 << 20))  # (12 B per row is the workload's pinned ceiling: tests/test_pack.py)
     res = [(np.full(n, RESULT_SENTINEL, np.uint8), np.zeros(n, np.uint64)) for _ in range(2)]
-    pinned = [getattr(host, c) for c in COLS] + [blob_buf] + [a for pair in res for a in pair]
+    res_buf = _aligned_bytes(results_bound(n))
+    ds, dv = np.zeros(n, np.uint8), np.zeros(n, np.uint64)  # the result blob decoded on the host
+    pinned = [getattr(host, c) for c in COLS] + [blob_buf, res_buf] + [a for pair in res for a in pair]
     for a in pinned:
         host_register(a)
     (sw, vw), (sp, vp) = res
-    ms = {"wide": [], "pack": [], "packed_call": []}
+    ms = {"wide": [], "pack": [], "packed_call": [], "packed_both": [], "unpack_results": []}
     chunks, bytes_per_row = [], []
+    chunks_both, result_bytes_per_row = [], []
     try:
         for step in range(args.warmup + args.repeats):
             clients.next(n, out=host)
@@ -95,10 +103,27 @@ def main():
             tc = _ms(lambda: EP.apply_host_packed(blob, n, events=False, chunk_rows=args.chunk_rows, out=(sp, vp),
                                                   timeline=True))
             assert np.array_equal(sw, sp) and np.array_equal(vw, vp), f"step {step}: the two paths' results differ"
+            rblob = None
+
+            def do_both():
+                nonlocal rblob
+                rblob = EB.apply_host_packed_results(blob, n, events=False, chunk_rows=args.chunk_rows, out=res_buf,
+                                                     timeline=True)[0]
+
+            tb = _ms(do_both)
+            assert results_check(rblob) == n
+            rr = abi.cc_results(ds.ctypes.data, dv.ctypes.data)
+            tu = _ms(lambda: _check(EB.L.cc_respack_unpack(rblob.ctypes.data, rblob.nbytes, C.byref(rr), args.threads)))
+            assert np.array_equal(sw, ds) and np.array_equal(vw, dv), f"step {step}: the decoded result blob differs"
+            print(f"step {step}: wide {tw:.2f} pack {tp:.2f} packed_call {tc:.2f} packed_both {tb:.2f} "
+                  f"unpack_results {tu:.2f} ms", file=sys.stderr, flush=True)
             if step >= args.warmup:
                 ms["wide"].append(tw), ms["pack"].append(tp), ms["packed_call"].append(tc)
+                ms["packed_both"].append(tb), ms["unpack_results"].append(tu)
                 chunks.append(EP.packed_timeline().tolist())
+                chunks_both.append(EB.packed_results_timeline().tolist())
                 bytes_per_row.append(len(blob) / n)
+                result_bytes_per_row.append(len(rblob) / n)
         last_info = pack_info(blob) if n <= (1 << 24) else None
         # once more from pageable memory: fresh copies nobody registered
         clients.next(n, out=host)
@@ -129,6 +154,18 @@ def main():
     out["decode_below_h2d_every_chunk"] = all(c[1] < c[0] for call in chunks for c in call)
     out["max_decode_over_h2d"] = round(max(c[1] / c[0] for call in chunks for c in call), 4)
     out["pageable"] = pageable
+    # packed results: per chunk of the median-time call [H2D, decode, apply, encode, D2H] ms; over every timed call and
+    # chunk, the encode time over the D2H time it saves against the wide-result call of the same step
+    out["ms_packed_both"] = _stat(ms["packed_both"])
+    out["ms_unpack_results"] = _stat(ms["unpack_results"])
+    out["result_bytes_per_row"] = round(statistics.median(result_bytes_per_row), 3)
+    out["wide_result_bytes_per_row"] = 9
+    out["packed_both_over_packed_call"] = round(out["ms_packed_both"]["median_ms"] / out["ms_packed_call"]["median_ms"], 4)
+    order = sorted(range(len(chunks_both)), key=lambda i: ms["packed_both"][i])
+    out["chunks_ms_h2d_decode_apply_encode_d2h"] = [[round(x, 3) for x in c] for c in chunks_both[order[len(order) // 2]]]
+    saved = [(cb[3], cw[3] - cb[4]) for wide_call, both_call in zip(chunks, chunks_both) for cw, cb in zip(wide_call, both_call)]
+    out["encode_below_d2h_saved_every_chunk"] = all(d > 0 and e < d for e, d in saved)
+    out["encode_over_d2h_saved"] = round(max(e / d for e, d in saved), 4) if all(d > 0 for _, d in saved) else None
     if last_info:
         out["columns_bytes_per_row"] = {k: v["bytes_per_row"] for k, v in last_info["columns"].items()}
     line = json.dumps(out)
