@@ -12,6 +12,8 @@
 // Reference semantics are AtomicValueState's (atomic/src/main/java/io/atomix/atomic/state/AtomicValueState.java):
 // get :77-83, set :114-118, compareAndSet :123-133, getAndSet :138-144, delete :146-157; dispatch and unknown
 // sessions ResourceManager.operateResource :56-72 (UNKNOWN_SESSION rows are answered by the unpermute).
+#include <type_traits>
+
 #include "common.h"
 #include "engine_internal.h"
 
@@ -152,11 +154,20 @@ __device__ inline uint64_t v3_pack_result(uint32_t status, uint64_t v, bool esc)
 // written out contiguously: every 128-byte line of the staging area is written whole by one instruction (k_part_v3
 // wrote each run piece per 2048-commit chunk, and lines shared by two pieces reached HBM as partial writes: 22.6 B
 // written per commit for 18).  Thread (w, j, l) holds commit w*512 + j*64 + l of the tile in registers (the
-// tile's rows are wave-contiguous, so per-wave lane-ordered counters give a stable rank); after the placement the
-// registers take the NEXT tile's loads, which are in flight while this tile's image is written out.
+// tile's rows are wave-contiguous, so per-wave lane-ordered counters give a stable rank).
+// The tile loop keeps the next tile's loads in flight through the tile's compute.  At the top of a tile, once its
+// columns have landed, the gathers of inst_res are issued and every row is encoded into its 8-byte record (slot 0,
+// the row set if escaped: nothing in the record needs the rank), which frees the raw column registers while the
+// gathers are still out; the next tile's columns are then loaded in two slices, one right there and one while wave 0
+// scans.  The placement only ORs the slot into the record.  The columns are loaded 16 bytes a lane (14 load
+// instructions a thread and tile, 28 as 4- and 8-byte loads: the tile's read time follows the number of load
+// instructions a CU has to get through, not their bytes) and change to the rank layout through 4 KB of LDS per wave.
+// Registers: 128 VGPRs, no scratch (16 of records beside the 44 of the raw next tile, so resource and rank share a
+// register); LDS 148,488 B, one workgroup per CU as before.
 // LDS hazards: each wave zeroes its own counter row at the top of a tile (its previous readers -- wave 0's scan and
 // the wave's own placement -- finished before the previous tile's B3); img / kst are rewritten only after the next
-// tile's B1 / B2, which every thread reaches after its own write-out reads.
+// tile's B1 / B2, which every thread reaches after its own write-out reads; stg[w] is wave w's alone (a wave's LDS
+// accesses execute in order).
 constexpr int kP4T = 1024;
 constexpr int kP4W = kP4T / kWave;    // 16 waves
 constexpr int kP4J = kV3Tile / kP4T;  // 8 commits per thread
@@ -172,157 +183,259 @@ __global__ __launch_bounds__(kP4T) void k_part_v4(const uint32_t* __restrict__ i
   __shared__ uint64_t img[kV3Tile];          // the tile's records in staging order
   __shared__ uint32_t wc[kP4W][kMaxSb / 2];  // per-wave counters (packed u16 pairs) -> per-wave exclusive prefixes
   __shared__ uint16_t kst[kMaxSb + 1];       // tile-local run starts (+ live count)
+  __shared__ uint64_t stg[kP4W][kWave * kP4J];  // per wave: one column of its 512 rows, from load layout to row layout
   const uint32_t t = threadIdx.x, w = t >> 6, l = t & 63;
   const uint32_t hw = (sb + 1) / 2;
   uint32_t T = blockIdx.x;
   if (T >= tiles) return;
   PH_DECL
-  // of2[j / 2] >> 16 * (j % 2) = op | flags << 8 of row j (two rows per register).  A full tile's op and flags columns arrive as 4-row words (opw / flw: lane l of
-  // wave w holds rows w*512 + i*256 + 4l .. +3), one load instruction per 256 rows instead of one per 64 (the 16
-  // byte loads per thread were issue-bound in the address unit: 19.4 -> 15.1 us per tile without them), and are
-  // spread to the rank layout (row w*512 + j*64 + l) by lane shuffles at the top of the tile; a partial tile or an
-  // unaligned column loads bytes.
-  uint32_t ri[kP4J], of2[kP4J / 2], opw[2], flw[2];
-  uint64_t av[kP4J], bv[kP4J];
-  bool wide = false;
+  // of2[j / 2] >> 16 * (j % 2) = op | flags << 8 of row j (two rows per register).  With 4-byte aligned op / flags
+  // columns (`wide`, a property of the launch) they arrive as 4-row words (lane l of wave w holds rows
+  // w*512 + i*256 + 4l .. +3), one load instruction per 256 rows instead of one per 64 (the 16 byte loads per
+  // thread were issue-bound in the address unit: 19.4 -> 15.1 us per tile without them), and are spread to the rank
+  // layout (row w*512 + j*64 + l) by lane shuffles at the top of the tile; unaligned columns load bytes.  The tile
+  // loop is compiled once for each form: a branch around loads inside the loop would make the counted waits behind
+  // it wait for the loads of both arms.
   const bool opfl_al = ((((uintptr_t)op) | ((uintptr_t)flags) | (uintptr_t)lo) & 3u) == 0;
-  auto rowq = [&](int j) -> uint32_t { return w * (kWave * kP4J) + (uint32_t)j * kWave + l; };
-  auto load = [&](uint32_t TT) {
-    const uint64_t t0 = lo + (uint64_t)TT * kV3Tile;
-    const uint32_t nr = (uint32_t)(hi - t0 < (uint64_t)kV3Tile ? hi - t0 : (uint64_t)kV3Tile);
-    wide = opfl_al && nr == (uint32_t)kV3Tile;  // block-uniform
-    if (wide) {
+  const uint32_t q0 = w * (kWave * kP4J) + l;  // row of j = 0; row of j = q0 + 64 j
+  // r[j]: the row's resource (< 2^17) | its rank among its wave's rows of the same super-bucket (< 512) << 17 from
+  // the rank on; kNoRes = no resource
+  constexpr uint32_t kResBits = 17;
+  static_assert(kMaxSb << KSB <= 1 << kResBits && kWave * kP4J <= 1 << (31 - kResBits), "k_part_v4 packs resource and rank");
+  // The next tile's loads go out in two slices: the instance column, op / flags and the first kS1 of the four
+  // operand loads right after the encode, the rest between B1 and B2.
+  constexpr int kS1 = 2, kOpLoads = kP4J / 2;
+  auto tile_loop = [&](auto wide_c) {
+    constexpr bool wide = decltype(wide_c)::value;
+    // ofr: a wide tile's op / flags words ({op 0, op 1, flags 0, flags 1}) until `unpack`; of2 from there on, and
+    // for byte loads from the start
+    // riw / aw / bw: the instance and operand columns as loaded, 16 bytes a lane: lane l of wave w holds rows
+    // w*512 + 256 i + 4l .. +3 of inst in riw[i] and rows w*512 + 128 m + 2l, +1 of a / b in aw[m] / bw[m].  A CU
+    // gets through its load instructions at a rate that does not depend on their width, so the
+    // columns come in as few instructions as their layout allows (14 a thread and tile instead of 28) and are turned to the rank layout (row
+    // w*512 + 64 j + l) through the wave's own 4 KB of `stg` at the top of the tile.
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 riw[2], aw[kP4J / 2], bw[kP4J / 2];
+    uint32_t ofr[kP4J / 2];
+    auto rowq = [&](int j) -> uint32_t { return q0 + (uint32_t)j * kWave; };
+    // row j is below n (q0 + 64 j < n, n <= 8192) with j on the scalar side: no per-row register
+    auto row_below = [&](int j, uint32_t n) -> bool { return (int)q0 < (int)n - j * kWave; };
+    // A tile's loads, in the order they are needed back (loads return in issue order): the instance column (the
+    // gathers wait for it alone), op / flags, then the operand loads m0 .. m1-1.  Buffer loads: one descriptor per
+    // column and tile (base = the tile's first row, size = its live rows; block-uniform), the thread's row as a
+    // 32-bit offset and j in the instruction's immediate, so a load takes no address registers, no clamp and no
+    // branch: a row past the batch end reads as 0 (ignored), and past the last tile the size is 0 and nothing is
+    // read.  (An aligned op / flags word that holds a live row is read whole, so its size is rounded up to 4; a
+    // 16-byte load is range-checked dword by dword, so the live rows of one that straddles the batch end arrive.)
+    uint64_t lt0 = 0;
+    uint32_t lnr = 0;
+    auto rsrc = [&](const void* col, uint32_t esz, uint32_t rows) {
+      return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(static_cast<const uint8_t*>(col)) + lt0 * esz, 0,
+                                               (int)(rows * esz), 0x00020000);
+    };
+    // (the thread's row as the tile loop sees it afresh: offsets computed ahead of the loop would each hold a
+    // register through it instead of folding into the instructions' immediates)
+    auto row0 = [&]() -> uint32_t {
+      uint32_t q = q0;
+      asm volatile("" : "+v"(q));
+      return q;
+    };
+    constexpr int kNt = 2;  // the nontemporal cache policy bit of a buffer load
+    auto load_head = [&](uint32_t TT) {
+      const bool live = TT < tiles;
+      lt0 = live ? lo + (uint64_t)TT * kV3Tile : lo;
+      lnr = live ? (uint32_t)(hi - lt0 < (uint64_t)kV3Tile ? hi - lt0 : (uint64_t)kV3Tile) : 0u;
+      const auto di = rsrc(inst, 4, lnr);
+      const uint32_t q = row0();
+      const uint32_t qw = q + 3u * (q & 63u);  // w * 512 + 4 l
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const uint64_t ic = t0 + w * (kWave * kP4J) + (uint32_t)i * (4 * kWave) + 4u * l;
-        opw[i] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(op + ic));
-        flw[i] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(flags + ic));
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < kP4J; ++j) {
-      const uint32_t q = rowq(j);
-      const uint64_t ic = t0 + (q < nr ? q : 0u);  // rows past the batch end re-read row 0 (ignored)
-      ri[j] = __builtin_nontemporal_load(inst + ic);
+      for (int i = 0; i < 2; ++i) riw[i] = __builtin_amdgcn_raw_buffer_load_b128(di, 4 * qw + i * (16 * kWave), 0, kNt);
 #ifdef CC_DIAG_NO_OPFL  // diagnostics build only: op / flags not loaded (wrong results; the byte loads' issue cost)
-      if (j % 2 == 0) of2[j / 2] = 0x11321132u;
+#pragma unroll
+      for (int j = 0; j < kP4J / 2; ++j) ofr[j] = 0x11321132u;
 #else
-      if (!wide) {
-        const uint32_t v = (uint32_t)__builtin_nontemporal_load(op + ic) | ((uint32_t)__builtin_nontemporal_load(flags + ic) << 8);
-        of2[j / 2] = j % 2 ? (of2[j / 2] | (v << 16)) : v;
+      if constexpr (wide) {
+        const auto dop = rsrc(op, 1, (lnr + 3u) & ~3u), dfl = rsrc(flags, 1, (lnr + 3u) & ~3u);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const uint32_t ic = qw + (uint32_t)i * (4 * kWave);  // w * 512 + 4 l + 256 i
+          ofr[i] = __builtin_amdgcn_raw_buffer_load_b32(dop, ic, 0, kNt);
+          ofr[2 + i] = __builtin_amdgcn_raw_buffer_load_b32(dfl, ic, 0, kNt);
+        }
+      } else {
+        const auto dop = rsrc(op, 1, lnr), dfl = rsrc(flags, 1, lnr);
+#pragma unroll
+        for (int j = 0; j < kP4J; ++j) {
+          const uint32_t v = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(dop, q + j * kWave, 0, kNt) |
+                             ((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(dfl, q + j * kWave, 0, kNt) << 8);
+          ofr[j / 2] = j % 2 ? (ofr[j / 2] | (v << 16)) : v;
+        }
       }
 #endif
-      av[j] = __builtin_nontemporal_load(ca + ic);
-      bv[j] = __builtin_nontemporal_load(cb + ic);
-    }
-  };
-  // (at the top of a tile: the words landed with the instance column the gathers there wait for)
-  auto unpack = [&]() {
+    };
+    auto load_ab = [&](int m0, int m1) {  // the operand loads m0 .. m1-1 of the four
+      const auto da = rsrc(ca, 8, lnr), db = rsrc(cb, 8, lnr);
+      const uint32_t q = row0();
+      const uint32_t q2 = q + (q & 63u);  // w * 512 + 2 l
+#pragma unroll
+      for (int m = m0; m < m1; ++m) {
+        aw[m] = __builtin_amdgcn_raw_buffer_load_b128(da, 8 * q2 + m * (16 * kWave), 0, kNt);
+        bw[m] = __builtin_amdgcn_raw_buffer_load_b128(db, 8 * q2 + m * (16 * kWave), 0, kNt);
+      }
+    };
+    // One column of the wave's 512 rows through its part of `stg`: written as loaded, read in the rank layout.  The
+    // wave's LDS accesses execute in order; the fences keep the compiler from moving a read over a write.
+    auto stg_fence = [&]() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront", "local"); };
+    // (at the top of a tile: the words landed with the instance column the gathers there wait for)
+    auto unpack = [&]() {
 #ifndef CC_DIAG_NO_OPFL
-    if (!wide) return;
+      if constexpr (wide) {
+        uint32_t o2[kP4J / 2];
 #pragma unroll
-    for (int j = 0; j < kP4J; ++j) {
-      const int src = (j % 4) * 16 + (int)(l >> 2);
-      const uint32_t sh = 8u * (l & 3u);
-      const uint32_t o = ((uint32_t)__shfl((int)opw[j / 4], src, kWave) >> sh) & 0xFFu;
-      const uint32_t f = ((uint32_t)__shfl((int)flw[j / 4], src, kWave) >> sh) & 0xFFu;
-      of2[j / 2] = j % 2 ? (of2[j / 2] | ((o | (f << 8)) << 16)) : (o | (f << 8));
-    }
+        for (int j = 0; j < kP4J; ++j) {
+          const int src = (j % 4) * 16 + (int)(l >> 2);
+          const uint32_t sh = 8u * (l & 3u);
+          const uint32_t o = ((uint32_t)__shfl((int)ofr[j / 4], src, kWave) >> sh) & 0xFFu;
+          const uint32_t f = ((uint32_t)__shfl((int)ofr[2 + j / 4], src, kWave) >> sh) & 0xFFu;
+          o2[j / 2] = j % 2 ? (o2[j / 2] | ((o | (f << 8)) << 16)) : (o | (f << 8));
+        }
+#pragma unroll
+        for (int j = 0; j < kP4J / 2; ++j) ofr[j] = o2[j];
+      }
 #endif
-  };
-  load(T);
-  for (;;) {
-    const uint64_t tile0 = lo + (uint64_t)T * kV3Tile;
-    const uint32_t tbase = T * kV3Tile;
-    const uint32_t nrow = (uint32_t)(hi - tile0 < (uint64_t)kV3Tile ? hi - tile0 : (uint64_t)kV3Tile);
-    for (uint32_t k = l; k < hw; k += kWave) wc[w][k] = 0;
-    uint32_t r[kP4J], loc[kP4J];
+    };
+    load_head(T);
+    load_ab(0, kOpLoads);
+    for (;;) {
+      const uint64_t tile0 = lo + (uint64_t)T * kV3Tile;
+      const uint32_t tbase = T * kV3Tile;
+      const uint32_t nrow = (uint32_t)(hi - tile0 < (uint64_t)kV3Tile ? hi - tile0 : (uint64_t)kV3Tile);
+      const uint32_t Tn = T + gridDim.x;
+      for (uint32_t k = l; k < hw; k += kWave) wc[w][k] = 0;
+      uint32_t r[kP4J], okm = 0;
+      uint64_t rec[kP4J];
+      {
+        u32x4* s4 = reinterpret_cast<u32x4*>(stg[w]);
+        const uint32_t* s1 = reinterpret_cast<const uint32_t*>(stg[w]);
+        s4[l] = riw[0];
+        s4[kWave + l] = riw[1];
+        stg_fence();
 #pragma unroll
-    for (int j = 0; j < kP4J; ++j) {  // instance -> resource (unconditional gathers, then the select)
-      const bool ok = rowq(j) < nrow && ri[j] < max_inst;
-      const uint32_t g = inst_res[ok ? ri[j] : 0u];
-      r[j] = ok ? g : kNoRes;
-    }
-    unpack();  // (while the gathers fly)
+        for (int j = 0; j < kP4J; ++j) {  // instance -> resource (unconditional gathers; the select comes at the rank)
+          const uint32_t ri = s1[j * kWave + l];
+          const bool ok = row_below(j, nrow) && ri < max_inst;
+          r[j] = inst_res[ok ? ri : 0u];
+          okm |= ok ? 1u << j : 0u;
+        }
+        stg_fence();
+      }
+      unpack();
+      uint64_t av[kP4J], bv[kP4J];
+      {
+        u32x4* s4 = reinterpret_cast<u32x4*>(stg[w]);
 #pragma unroll
-    for (int j = 0; j < kP4J; ++j) {
-      const uint32_t k = r[j] >> KSB, sh = 16 * (k & 1);
-      loc[j] = r[j] != kNoRes ? (atomicAdd(&wc[w][k >> 1], 1u << sh) >> sh) & 0xFFFFu : 0xFFFFu;
-    }
-    PH(0);
-    lds_barrier();  // B1: counters complete
-    PH(1);
-    if (w == 0) {   // per super-bucket: exclusive prefix over the waves (in place), totals, tile-local run starts
-      uint32_t tot[KP];
+        for (int m = 0; m < kP4J / 2; ++m) s4[m * kWave + l] = aw[m];
+        stg_fence();
 #pragma unroll
-      for (int e = 0; e < KP; e += 2) {
-        const uint32_t pr = (l * KP + e) / 2;
-        uint32_t acc = 0;
-        if (pr < hw) {
+        for (int j = 0; j < kP4J; ++j) av[j] = stg[w][j * kWave + l];
+        stg_fence();
 #pragma unroll
-          for (int q = 0; q < kP4W; ++q) {
-            const uint32_t x = wc[q][pr];
-            wc[q][pr] = acc;
-            acc += x;
+        for (int m = 0; m < kP4J / 2; ++m) s4[m * kWave + l] = bw[m];
+        stg_fence();
+#pragma unroll
+        for (int j = 0; j < kP4J; ++j) bv[j] = stg[w][j * kWave + l];
+        stg_fence();
+      }
+      // (while the gathers fly) every row's record with slot 0, its row set if escaped: nothing in it needs the rank
+#pragma unroll
+      for (int j = 0; j < kP4J; ++j) {
+        const uint32_t ofj = ofr[j / 2] >> (16 * (j % 2));
+        rec[j] = v3_set_row(v3_encode(ofj & 0xFFu, (ofj >> 8) & 0xFFu, av[j], bv[j], 0), rowq(j));
+        asm volatile("" : "+v"(rec[j]));  // the finished word, here: its parts must not stay live beside the next tile
+      }
+      // the raw registers are free: the next tile's loads fly through the rest of this tile
+      load_head(Tn);
+      load_ab(0, kS1);
+#pragma unroll
+      for (int j = 0; j < kP4J; ++j) {
+        const uint32_t g = (okm >> j) & 1u ? r[j] : kNoRes;
+        const uint32_t k = g >> KSB, sh = 16 * (k & 1);
+        r[j] = g != kNoRes ? g | (((atomicAdd(&wc[w][k >> 1], 1u << sh) >> sh) & 0xFFFFu) << kResBits) : kNoRes;
+      }
+      PH(0);
+      lds_barrier();  // B1: counters complete
+      PH(1);
+      if (w == 0) {   // per super-bucket: exclusive prefix over the waves (in place), totals, tile-local run starts
+        uint32_t tot[KP];
+#pragma unroll
+        for (int e = 0; e < KP; e += 2) {
+          const uint32_t pr = (l * KP + e) / 2;
+          uint32_t acc = 0;
+          if (pr < hw) {
+#pragma unroll
+            for (int q = 0; q < kP4W; ++q) {
+              const uint32_t x = wc[q][pr];
+              wc[q][pr] = acc;
+              acc += x;
+            }
           }
+          tot[e] = acc & 0xFFFFu;
+          tot[e + 1] = acc >> 16;
         }
-        tot[e] = acc & 0xFFFFu;
-        tot[e + 1] = acc >> 16;
-      }
-      uint32_t mine = 0;
+        uint32_t mine = 0;
 #pragma unroll
-      for (int e = 0; e < KP; ++e) mine += tot[e];
-      uint32_t inc = mine;
+        for (int e = 0; e < KP; ++e) mine += tot[e];
+        uint32_t inc = mine;
 #pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(inc, d, 64);
-        if (l >= (uint32_t)d) inc += y;
-      }
-      uint32_t run = inc - mine;
-      uint16_t* row = ttab + (uint64_t)T * (sb + 1);
-#pragma unroll
-      for (int e = 0; e < KP; ++e) {
-        const uint32_t k = l * KP + e;
-        if (k < sb) {
-          kst[k] = (uint16_t)run;
-          row[k] = (uint16_t)run;
+        for (int d = 1; d < 64; d <<= 1) {
+          const uint32_t y = __shfl_up(inc, d, 64);
+          if (l >= (uint32_t)d) inc += y;
         }
-        run += tot[e];
-      }
-      if (l == 63) {
-        kst[sb] = (uint16_t)inc;
-        row[sb] = (uint16_t)inc;
-      }
-    }
-    PH(2);
-    lds_barrier();  // B2: prefixes and run starts
-    PH(3);
+        uint32_t run = inc - mine;
+        uint16_t* row = ttab + (uint64_t)T * (sb + 1);
 #pragma unroll
-    for (int j = 0; j < kP4J; ++j) {
-      const uint32_t q = rowq(j);
-      uint32_t cp = 0xFFFFu;
-      if (loc[j] != 0xFFFFu) {
-        const uint32_t k = r[j] >> KSB, sh = 16 * (k & 1);
-        const uint32_t sp = kst[k] + ((wc[w][k >> 1] >> sh) & 0xFFFFu) + loc[j];
-        const uint32_t ofj = of2[j / 2] >> (16 * (j % 2));
-        img[sp] = v3_set_row(v3_encode(ofj & 0xFFu, (ofj >> 8) & 0xFFu, av[j], bv[j], r[j] & ((1u << KSB) - 1)), q);
-        cp = sp;
+        for (int e = 0; e < KP; ++e) {
+          const uint32_t k = l * KP + e;
+          if (k < sb) {
+            kst[k] = (uint16_t)run;
+            row[k] = (uint16_t)run;
+          }
+          run += tot[e];
+        }
+        if (l == 63) {
+          kst[sb] = (uint16_t)inc;
+          row[sb] = (uint16_t)inc;
+        }
       }
-      if (q < nrow) cpos[tbase + q] = (uint16_t)cp;
-    }
-    const uint32_t Tn = T + gridDim.x;
-    if (Tn < tiles) load(Tn);  // the raw registers are free: the next tile's loads fly during the write-out
-    PH(4);
-    lds_barrier();             // B3: the image is complete
-    PH(5);
-    // whole tile region, unconditionally (a fixed store count; rows past the live count are never read), 16 B a lane
+      load_ab(kS1, kOpLoads);  // the second slice: waves 1-15 issue it while wave 0 scans, wave 0 after its scan
+      PH(2);
+      lds_barrier();  // B2: prefixes and run starts
+      PH(3);
 #pragma unroll
-    for (int m = 0; m < kP4J / 2; ++m)
-      reinterpret_cast<uint4*>(st_rec + tbase)[t + m * kP4T] = reinterpret_cast<const uint4*>(img)[t + m * kP4T];
-    PH(6);
-    if (Tn >= tiles) break;
-    T = Tn;
-  }
+      for (int j = 0; j < kP4J; ++j) {
+        uint32_t cp = 0xFFFFu;
+        if (r[j] != kNoRes) {
+          const uint32_t k = (r[j] & ((1u << kResBits) - 1)) >> KSB, sh = 16 * (k & 1);
+          const uint32_t sp = kst[k] + ((wc[w][k >> 1] >> sh) & 0xFFFFu) + (r[j] >> kResBits);
+          img[sp] = rec[j] | (r[j] & ((1u << KSB) - 1));
+          cp = sp;
+        }
+        if (row_below(j, nrow)) cpos[tbase + rowq(j)] = (uint16_t)cp;
+      }
+      PH(4);
+      lds_barrier();             // B3: the image is complete
+      PH(5);
+      // whole tile region, unconditionally (a fixed store count; rows past the live count are never read), 16 B a lane
+#pragma unroll
+      for (int m = 0; m < kP4J / 2; ++m)
+        reinterpret_cast<uint4*>(st_rec + tbase)[t + m * kP4T] = reinterpret_cast<const uint4*>(img)[t + m * kP4T];
+      PH(6);
+      if (Tn >= tiles) break;
+      T = Tn;
+    }
+  };
+  if (opfl_al) tile_loop(std::true_type{});
+  else tile_loop(std::false_type{});
 #ifdef CC_PHASE_TIMING
   PH_FLUSH(g_ph_v3p);
 #endif

@@ -74,8 +74,10 @@ def run(args):
     launches = args.steps * ((n + sub - 1) // sub)
     tiles = (n + 16383) // 16384
     if os.environ.get("CC_V3_PHASES"):  # value_path.hip: k_part_v4 (one 1024-thread workgroup per CU, 8192-commit tiles)
-        PHASES[0] = ["loads wait+gather+rank", "B1", "wave-0 scan", "B2", "place+cpos+issue next",
-                     "B3", "write-out", "-"]
+        # (the next tile's loads are issued in phase 0, after the encode, and in phase 2; phase 7 is the issue of
+        # what a build leaves for after the placement: all of them before the early loads, profiles/part_pipe/parent)
+        PHASES[0] = ["loads wait+gather+encode+issue next+rank", "B1", "wave-0 scan+issue next", "B2", "place+cpos",
+                     "B3", "write-out", "issue next (after the placement)"]
         tiles = (n + 8191) // 8192
     wgs = {0: tiles * args.steps, 1: 256 * launches, 2: min(tiles, 256) * launches}
     names = {0: "k_part_tile", 1: "k_apply_value", 2: "k_unpermute"}
