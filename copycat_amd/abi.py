@@ -6,7 +6,7 @@ import ctypes as C
 
 CC_ABI_VERSION = 6
 CC_MEMCPY_H2D, CC_MEMCPY_D2H, CC_MEMCPY_D2D = 1, 2, 3
-CC_PROFILE_KERNELS = 7
+CC_PROFILE_KERNELS = 8
 CC_PHASES = 8  # phase clocks per kernel of the diagnostics build (cc_debug_phases)
 
 CC_OK = 0
@@ -25,6 +25,7 @@ CC_RES_GROUP = 5
 CC_RES_SET = 6
 CC_RES_QUEUE = 7
 CC_RES_MULTIMAP = 8
+CC_RES_TOPIC = 9
 CC_QUEUE_CAP = 64
 
 CC_OP_DELETE = 1
@@ -82,6 +83,9 @@ CC_OP_GROUP_JOIN = 120
 CC_OP_GROUP_LEAVE = 121
 CC_OP_GROUP_SCHEDULE = 122
 CC_OP_GROUP_EXECUTE = 123
+CC_OP_TOPIC_LISTEN = 125
+CC_OP_TOPIC_UNLISTEN = 126
+CC_OP_TOPIC_PUBLISH = 127
 
 CC_TAG_NULL = 0
 CC_TAG_LONG = 1
@@ -108,6 +112,7 @@ CC_EV_JOIN = 4
 CC_EV_LEAVE = 5
 CC_EV_EXECUTE = 6
 CC_EV_MEMBER = 7
+CC_EV_MESSAGE = 8
 
 CC_EVSRC_COMMIT = 0
 CC_EVSRC_TIMER = 1
@@ -121,6 +126,7 @@ CC_LOCK_QUEUE = 64
 CC_ELECTION_LISTENERS = 64
 CC_GROUP_MEMBERS = 64
 CC_VALUE_LISTENERS = 64
+CC_TOPIC_LISTENERS = 64
 
 # ops each resource type registers (ResourceStateMachine.init + Copycat reflection `configure`)
 TYPE_OPS = {
@@ -133,6 +139,8 @@ TYPE_OPS = {
     CC_RES_QUEUE: {CC_OP_DELETE} | set(range(90, 100)),
     CC_RES_MULTIMAP: {CC_OP_DELETE, 75} | set(range(78, 85)),
 }
+# TopicState's ops (TopicCommands.java:53,64,80); kept beside TYPE_OPS, whose ops the wire fixture must all contain
+TOPIC_OPS = {CC_OP_DELETE, 125, 126, 127}
 # key tags of the flags column (keys are never null)
 KTAG_OF_TAG = {CC_TAG_LONG: 0, CC_TAG_INT: 1, CC_TAG_BOOL: 2, CC_TAG_HANDLE: 3}
 TAG_OF_KTAG = {v: k for k, v in KTAG_OF_TAG.items()}

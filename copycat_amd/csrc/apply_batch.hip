@@ -1106,7 +1106,19 @@ int Batch::sub_coord(Sub& s) {
   ca.leak = e->d_leak;
   ca.leak_n = e->d_leak_n;
   ca.leak_cap = e->leak_cap;
-  return launched(launch_apply_coord(ca, st), "coordination apply launch", st);
+  ca.fx = e->d_fan;
+  if (!e->has_topics) return launched(launch_apply_coord(ca, st), "coordination apply launch", st);
+  // TopicState.publish: the walk leaves one fan record per publish, k_topic_fanout expands them into the arena
+  HIPCHECK(hipMemsetAsync(e->d_fan, 0, offsetof(FanCtx, cap), st));
+  TRY(launched(launch_apply_coord(ca, st), "coordination apply launch", st));
+  FanoutArgs fa{};
+  fa.fx = e->d_fan;
+  fa.arena = e->d_arena;
+  fa.arena_n = e->d_arena_n;
+  fa.arena_cap = e->arena_cap;
+  fa.err = e->d_err;
+  fa.mark = marker_of(e);
+  return launched(launch_topic_fanout(fa, st), "topic fan-out launch", st);
 }
 
 // the sub-batch's results back to log order (every staged result is written by then)

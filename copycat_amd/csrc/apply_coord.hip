@@ -1,5 +1,5 @@
-// apply_coord.hip — coordination state machines (LockState, LeaderElectionState, MembershipGroupState) and
-// AtomicValue with listeners, with their published events.
+// apply_coord.hip — coordination state machines (LockState, LeaderElectionState, MembershipGroupState, QueueState,
+// TopicState) and AtomicValue with listeners, with their published events.
 //
 // Like apply_value.hip, one thread owns one resource slot and applies that slot's commits in log order; here a
 // workgroup owns a quarter super-bucket (64 slots, see k_apply_coord).  The super-buckets handled here are those holding a
@@ -19,7 +19,10 @@
 //   LeaderElectionState.listen :57-66, unlisten :71-91, isLeader :96-98 (epoch not serialized -> 0, A3),
 //   delete :100-108;  MembershipGroupState.join :47-64 (Set<Long> result), leave :69-81, execute :108-119,
 //   delete :121-125 (schedule :86-103 is a timer with a payload: not applied on the GPU);
-//   AtomicValueState.listen :41-49, unlisten :54-63, change :68-72, get/set/compareAndSet/getAndSet :77-144.
+//   AtomicValueState.listen :41-49, unlisten :54-63, change :68-72, get/set/compareAndSet/getAndSet :77-144;
+//   TopicState.listen :42-48 (a second listen of an instance is clean()ed, the first stays), unlisten :53-62,
+//   publish :67-82 (one "message" per listener: not emitted here but left as one fan record for k_topic_fanout,
+//   topic_fanout.hip), delete :85-88, close :35-37 (close.hip).
 // Lock timeouts: a waiter whose deadline (clock at lock + timeout) is <= the clock at which due timers fire
 // before a commit (the previous commit's clock in manager mode, this commit's in module mode, A8) is gone
 // before that commit is applied; they publish nothing, so applying them lazily per lock is exact.
@@ -66,6 +69,7 @@ struct Emitter {
   LeakRec* leak;     // the engine's leak log (commits dropped without clean())
   unsigned long long* leak_n;
   uint64_t leak_cap;
+  FanCtx* fx;        // TopicState.publish: the sub-batch's fan records and listener log (k_topic_fanout)
   __device__ void leaked(uint32_t slot, uint64_t idx, uint32_t& err) const {
     const unsigned long long a = atomicAdd(leak_n, 1ull);
     if (a < leak_cap) {
@@ -613,6 +617,71 @@ __device__ inline uint32_t coord_apply(uint32_t type_rt, uint32_t slot, const Re
       rv = rvv;
       return CC_STATUS(CC_ST_OK, rtag);
     }
+    case CC_RES_TOPIC: {  // TopicState.java:31-90
+      // listeners: a HashMap keyed by commit.session().id(), the instance's ManagedResourceSession whose id() is the
+      // instance id (ManagedResourceSession.java:59-61); kept sorted by instance id like a group's members.  Every
+      // result is void.
+      if (r.op == CC_OP_DELETE) {  // delete :85-88: every listener commit clean()ed, the map emptied
+        h.n = 0;
+        h.flags &= ~kCoSnap;
+        return CC_STATUS(CC_ST_OK, CC_TAG_NULL);
+      }
+      if (r.op == CC_OP_TOPIC_PUBLISH) {
+        // publish :67-82: "message"(message) to every listener's session, the publish commit clean()ed.  The
+        // !isOpen() branch (:74-77) never runs here: a ManagedResourceSession leaves OPEN only when its parent session
+        // closes (:129-131), which the engine applies as cc_sessions_close / cc_sessions_expire, whose fan-out runs
+        // TopicState.close for the instance in the same step (close.hip): no listener of a closed session is left.
+        // The events go out in ascending listener instance id, emission index = rank (engine-defined: the
+        // reference iterates a HashMap, and each event of a publish goes to a different session, so no session
+        // observes an order between them).  The walk does not loop over the listeners to emit: it counts them
+        // (ev_cnt = n) and leaves one FanRec; k_topic_fanout writes the n events.  The listeners' instance slots as
+        // they stand now are in the listener log: copied by the topic's first publish of the launch and by the first
+        // one after a listen / unlisten that changed the list (kCoSnap clear), reused by the publishes in between.
+        const uint32_t n = h.n;
+        if (n) {
+          FanCtx* fx = em.fx;
+          if (!(h.flags & kCoSnap)) {  // one atomic per snapshot
+            const unsigned long long o = atomicAdd(&fx->log_n, (unsigned long long)n);
+            if (o + n <= fx->cap) {
+              uint32_t* lg = fx->log + o;
+              for (uint32_t i = 0; i < n; ++i) lg[i] = E.get(i).inst;
+              h.who = (uint32_t)o;
+              h.flags |= kCoSnap;
+            }
+          }
+          const unsigned long long q = atomicAdd(&fx->rec_n, 1ull);  // one atomic per record
+          if ((h.flags & kCoSnap) && q < fx->cap) {  // (else more events than the arena holds: k_topic_fanout fails the call)
+            const uint32_t tg = CC_FLAG_TAG_A(r.flags);
+            fx->rec[q] = FanRec{r.g, n, tg == CC_TAG_NULL ? 0 : r.a, h.who, tg};
+          }
+        }
+        nev = n;
+        return CC_STATUS(CC_ST_OK, CC_TAG_NULL);
+      }
+      // listen :42-48 / unlisten :53-62: the committing instance's entry (the group's sorted search and shifts)
+      uint32_t lo = 0, hi = h.n;
+      while (lo < hi) {
+        const uint32_t m = (lo + hi) >> 1;
+        if (E.get(m).x < r.iid) lo = m + 1; else hi = m;
+      }
+      const bool hit = lo < h.n && E.get(lo).x == r.iid;
+      const bool listen = r.op == CC_OP_TOPIC_LISTEN;
+      // a commit's event count is 16 bits (ev_cnt, EvRec.k): at coord_cap 65,536 a topic holds 65,535 listeners
+      const bool full = h.n == E.cap || h.n == 0xFFFFu;
+      if (listen && !hit && full) err |= kErrCoordFull;
+      if (listen && !hit && !full) {  // no entry: store the commit (an existing one stays; the new commit is clean()ed)
+        for (uint32_t i = h.n; i > lo; --i) E.put(i, E.get(i - 1));
+        E.put(lo, CoordEnt{r.iid, r.idx, r.inst, 0});
+        ++h.n;
+        h.flags &= ~kCoSnap;
+      }
+      if (!listen && hit) {  // listeners.remove + listener.clean()
+        for (uint32_t i = lo + 1; i < h.n; ++i) E.put(i - 1, E.get(i));
+        --h.n;
+        h.flags &= ~kCoSnap;
+      }
+      return CC_STATUS(CC_ST_OK, CC_TAG_NULL);
+    }
   }
   return CC_STATUS(CC_ST_UNKNOWN_OP, CC_TAG_NULL);
 }
@@ -655,7 +724,7 @@ __global__ __launch_bounds__(kCT2, 3) void k_apply_coord(const XRec* __restrict_
                                                      EvRec* __restrict__ arena, unsigned long long* __restrict__ arena_n,
                                                      uint64_t arena_cap, LeakRec* __restrict__ leak,
                                                      unsigned long long* __restrict__ leak_n, uint64_t leak_cap,
-                                                     uint32_t* __restrict__ err_out) {
+                                                     FanCtx* __restrict__ fx, uint32_t* __restrict__ err_out) {
   __shared__ u64x2 rab[kCCh2];
   __shared__ uint64_t rkey[kCCh2];
   __shared__ uint64_t ridx[kCCh2];
@@ -717,7 +786,7 @@ __global__ __launch_bounds__(kCT2, 3) void k_apply_coord(const XRec* __restrict_
   }
   const uint32_t cnt = rpre[tiles];
   static_assert(kQ == (int)kLanes, "one walking lane per slot of the quarter bucket");
-  const Emitter em{(LdsU64*)(evp + l), kEvLane, arena, arena_n, arena_cap, leak, leak_n, leak_cap};
+  const Emitter em{(LdsU64*)(evp + l), kEvLane, arena, arena_n, arena_cap, leak, leak_n, leak_cap, fx};
   // the walker lanes (wave 0, lane = slot) keep their state machine's header in registers for the whole launch
   const uint32_t res = s * (1u << kSbShift) + q0 + l;
   uint8_t* blk = coord + (uint64_t)res * coord_block(coord_cap);
@@ -913,6 +982,7 @@ __global__ __launch_bounds__(kCT2, 3) void k_apply_coord(const XRec* __restrict_
       else if (wt == CC_RES_ELECTION) walk(TypeC<CC_RES_ELECTION>{});
       else if (wt == CC_RES_GROUP) walk(TypeC<CC_RES_GROUP>{});
       else if (wt == CC_RES_VALUE) walk(TypeC<CC_RES_VALUE>{});
+      else if (wt == CC_RES_TOPIC) walk(TypeC<CC_RES_TOPIC>{});
       else walk(TypeC<0>{});
 #ifdef CC_PHASE_TIMING
       ev_total_lane += lane_n;
@@ -971,6 +1041,10 @@ __global__ __launch_bounds__(kCT2, 3) void k_apply_coord(const XRec* __restrict_
   if (w == 0) {
     E.store();
     CoordHdr* hp = reinterpret_cast<CoordHdr*>((uintptr_t)E.glb - sizeof(CoordHdr));  // (= blk)
+    if (type == CC_RES_TOPIC) {  // the snapshot offset and its flag live for one launch (kCoSnap)
+      h.who = 0;
+      h.flags &= ~kCoSnap;
+    }
     hp->who = h.who;
     hp->flags = h.flags;
     hp->idx = h.idx;
@@ -1004,7 +1078,7 @@ int launch_apply_coord(const CoordArgs& a, hipStream_t st) {
   a.mark(K_APPLY_COORD, 1, st);
   hipLaunchKernelGGL(k_apply_coord, dim3(a.sb_val * kQPerSb), dim3(kCT2), 0, st, a.xrec,
                      a.ttab, a.tiles, a.sb, a.sbq_base, a.sb_kind, a.res_type, a.inst_id, a.coord, a.coord_cap, a.val_meta, a.val_v, a.rst_status,
-                     a.rst_value, a.ev_cnt, a.arena, a.arena_n, a.arena_cap, a.leak, a.leak_n, a.leak_cap, a.err);
+                     a.rst_value, a.ev_cnt, a.arena, a.arena_n, a.arena_cap, a.leak, a.leak_n, a.leak_cap, a.fx, a.err);
   a.mark(K_APPLY_COORD, 0, st);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

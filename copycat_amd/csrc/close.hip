@@ -126,6 +126,24 @@ __global__ void k_close_apply(const uint32_t* __restrict__ cinst, const uint32_t
         --h.n;
       }
       for (uint32_t i = 0; i < h.n; ++i) ev(E[i].inst, CC_EV_LEAVE, iid);
+    } else if (type == CC_RES_TOPIC) {  // TopicState.close :35-37 (listeners sorted by instance id): no event
+      uint32_t lo = 0, hi = h.n;
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (E[mid].x < iid) lo = mid + 1; else hi = mid;
+      }
+      if (lo < h.n && E[lo].x == iid) {  // listeners.remove without clean(): the listen commit stays in the log
+        const unsigned long long a = atomicAdd(leak_n, 1ull);
+        if (a < leak_cap) {
+          leak[a].idx = E[lo].idx;
+          leak[a].slot = r;
+          leak[a].pad = 0;
+        } else {
+          atomicOr(err, kErrCapacity);
+        }
+        for (uint32_t j = lo + 1; j < h.n; ++j) E[j - 1] = E[j];
+        --h.n;
+      }
     }
     cnt[p] = nev;
   }

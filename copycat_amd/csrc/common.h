@@ -147,6 +147,7 @@ __host__ __device__ inline bool op_registered(uint32_t type, uint32_t op) {
     case CC_RES_SET: return op >= 100 && op <= 105;
     case CC_RES_QUEUE: return op >= 90 && op <= 99;
     case CC_RES_MULTIMAP: return op == 75 || (op >= 78 && op <= 84);  // MultiMapState.java:37-207 (no 76 / 77)
+    case CC_RES_TOPIC: return op >= 125 && op <= 127;  // TopicCommands.java:53,64,80
   }
   return false;
 }
@@ -201,6 +202,7 @@ __host__ __device__ inline bool op_on_gpu(uint32_t type, uint32_t op) {
   if (type == CC_RES_QUEUE) return op_registered(type, op);
   if (type == CC_RES_LOCK || type == CC_RES_ELECTION) return op_registered(type, op);
   if (type == CC_RES_GROUP) return op_registered(type, op);  // schedule rows are batch barriers (engine.hip)
+  if (type == CC_RES_TOPIC) return op_registered(type, op);  // publish: k_apply_coord + k_topic_fanout
   return false;
 }
 
@@ -247,6 +249,9 @@ constexpr uint32_t kCoHeld = 1u, kCoCleaned = 2u;
 // election whose holder commit was already cleaned): its instances stay registered and every commit on them hits
 // `resources.get(...) == null` -> NullPointerException (ResourceManager.java:62,71); close skips its handler
 constexpr uint32_t kCoZombie = 4u;
+// TopicState, inside one k_apply_coord launch only (never in a stored block): the walking lane's listener list has a
+// snapshot in the sub-batch's listener log, at word CoordHdr.who (a topic uses neither `who` nor `idx`)
+constexpr uint32_t kCoSnap = 8u;
 constexpr uint64_t kNoDeadline = ~0ull;
 // QueueState entry (CoordEnt.pad = value tag | kQCleaned): element() clean()ed the head it leaves in place
 // (QueueState.java:111-124), so the log no longer retains that commit
@@ -272,6 +277,7 @@ __host__ __device__ inline bool adds_entry(uint8_t type, uint8_t op, uint64_t au
     case CC_RES_GROUP: return op == CC_OP_GROUP_JOIN;
     case CC_RES_VALUE: return op == CC_OP_VALUE_LISTEN;
     case CC_RES_QUEUE: return op == CC_OP_QUEUE_ADD || op == CC_OP_QUEUE_OFFER;
+    case CC_RES_TOPIC: return op == CC_OP_TOPIC_LISTEN;
     default: return false;
   }
 }
@@ -337,6 +343,29 @@ struct EvRec {
   uint64_t payload;
   uint16_t k;       // emission order within the commit
   uint8_t code, tag, src, pad[3];
+};
+// One TopicState.publish (TopicState.java:67-82) as k_apply_coord leaves it for k_topic_fanout (topic_fanout.hip): the
+// walk writes ev_cnt[g] = n and this record; the expansion kernel writes the n EvRecs {g, log[snap + i], payload,
+// k = i, CC_EV_MESSAGE, tag, CC_EVSRC_COMMIT}.  log = the sub-batch's listener log: the instance slots of the topic's
+// listeners (ascending instance id) as they stood at the publish row.
+struct FanRec {
+  uint32_t g;       // staging position of the publish commit
+  uint32_t n;       // listeners at that row (> 0: a publish to nobody leaves no record)
+  uint64_t payload; // the canonical message (0 for NULL)
+  uint32_t snap;    // first word of the listeners' snapshot in the listener log
+  uint32_t tag;     // the message's tag
+};
+static_assert(sizeof(FanRec) == 24, "FanRec is three 8-byte words");
+// The sub-batch's fan records and listener log (device memory; the counters are zeroed per sub-batch).  A snapshot of
+// n words is always followed by a publish of n events, and a record stands for at least one event, so neither list
+// holds more entries than the sub-batch has events: both are sized like the event arena (cap), and one that overflows
+// means the arena does too (kErrEvents).
+struct FanCtx {
+  unsigned long long rec_n;  // fan records appended (may pass cap: the excess is dropped and the call fails)
+  unsigned long long log_n;  // listener-log words reserved
+  uint64_t cap;              // records in `rec` = words in `log` = the event arena's capacity
+  FanRec* rec;
+  uint32_t* log;
 };
 constexpr uint32_t kErrTime = 8u;  // the time column decreased inside a batch
 constexpr uint32_t kErrMapOrder = 16u;  // containsValue's HashMap iteration order is undetermined (map_wide.hip)

@@ -104,7 +104,7 @@ static void free_all(cc_engine* e) {
                   e->d_cvset,    e->d_cvcnt,    e->d_cvev_key, e->d_cvev_key2, e->d_cvev_val, e->d_cvev_val2, e->d_cvev_ctl,
                   e->d_cvseg,    e->d_cvtemp,   e->d_clrq,    e->d_clrq_n,   e->d_clr_keys,   e->d_clr_keys2, e->d_clr_off,
                   e->d_clr_base, e->d_clr_eend, e->d_clr_temp, e->d_tbl_ep, e->d_clr_scan, e->d_clr_stemp, e->d_clr_btab, e->d_cvbloom,
-                  e->d_px,       e->d_px_bcnt,  e->d_px_evn};
+                  e->d_px,       e->d_px_bcnt,  e->d_px_evn,   e->d_fan};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void*& p : e->hw_buf)
@@ -178,8 +178,16 @@ static int ensure_ext(cc_engine* e, bool coord) {
         (rc = alloc((void**)&e->d_ev_ccnt, sizeof(uint32_t) * ev_chunk_cap(e->arena_cap) * e->max_tiles)) ||
         (rc = alloc((void**)&e->d_arena_n, sizeof(unsigned long long))) ||
         (rc = alloc((void**)&e->d_ev_total, sizeof(unsigned long long))) ||
+        (rc = alloc((void**)&e->d_fan, sizeof(FanCtx))) ||
         (rc = ensure_leak(e, kLeakCap)))
       return rc;
+    {  // TopicState.publish: fan records over d_ev_bucket, the listener log over d_ev_perm (u32 offsets)
+      const FanCtx fx{0, 0, std::min<uint64_t>(e->arena_cap, 0xFFFFFFFFull), reinterpret_cast<FanRec*>(e->d_ev_bucket),
+                      e->d_ev_perm};
+      static_assert(sizeof(FanRec) == sizeof(EvRec), "the fan records share the order pass's bucket array");
+      hipError_t y = hipMemcpy(e->d_fan, &fx, sizeof fx, hipMemcpyHostToDevice);
+      if (y != hipSuccess) return set_err(CC_ERR_HIP, "fan context upload", y);
+    }
     hipError_t x = hipMemset(e->d_coord, 0, coord_block(e->coord_cap) * slots);
     if (x != hipSuccess) return set_err(CC_ERR_HIP, "memset coord", x);
     e->coord_on = true;
@@ -190,7 +198,8 @@ static int ensure_ext(cc_engine* e, bool coord) {
 }
 
 static bool is_coord(uint32_t type) {
-  return type == CC_RES_LOCK || type == CC_RES_ELECTION || type == CC_RES_GROUP || type == CC_RES_QUEUE;
+  return type == CC_RES_LOCK || type == CC_RES_ELECTION || type == CC_RES_GROUP || type == CC_RES_QUEUE ||
+         type == CC_RES_TOPIC;
 }
 
 extern "C" int cc_abi_version(void) { return CC_ABI_VERSION; }
@@ -561,9 +570,10 @@ int cc::dev_flush(cc_engine* e) {
 
 int cc::create_range(cc_engine* e, uint32_t first, uint32_t count, uint32_t type) {
   if (is_keyed(type) && !e->map_bits) return set_err(CC_ERR_CAPACITY, "map and set resources need cc_config.map_capacity > 0");
-  if (type < CC_RES_VALUE || type > CC_RES_MULTIMAP) return set_err(CC_ERR_INVALID, "unknown resource type");
+  if (type < CC_RES_VALUE || type > CC_RES_TOPIC) return set_err(CC_ERR_INVALID, "unknown resource type");
   if (type == CC_RES_SET) e->has_sets = true;
   if (type == CC_RES_VALUE) e->has_values = true;
+  if (type == CC_RES_TOPIC) e->has_topics = true;
   if (type == CC_RES_MULTIMAP) {
     e->has_mmaps = true;
     int rc = ensure_leak(e, kLeakCap);
@@ -898,7 +908,7 @@ static int sessions_close_core(cc_engine* e, const std::vector<std::pair<uint64_
     HIPCHECK(hipStreamSynchronize(st));
     return CC_OK;
   }
-  // positions grouped by resource (only state machines with a close handler: value, election, group)
+  // positions grouped by resource (only state machines with a close handler: value, election, group, topic)
   std::vector<uint32_t> cinst(m), rlist, rstart, items;
   std::vector<std::pair<uint32_t, uint32_t>> rp;
   for (uint32_t p = 0; p < m; ++p) {
@@ -907,7 +917,7 @@ static int sessions_close_core(cc_engine* e, const std::vector<std::pair<uint64_
     const uint8_t ty = e->res_type[r];
     // a resource a failed deleteResource left behind is not in `resources` any more: no close handler (:253-257)
     if (e->res_zombie[r]) continue;
-    if (ty == CC_RES_VALUE || ty == CC_RES_ELECTION || ty == CC_RES_GROUP) rp.emplace_back(r, p);
+    if (ty == CC_RES_VALUE || ty == CC_RES_ELECTION || ty == CC_RES_GROUP || ty == CC_RES_TOPIC) rp.emplace_back(r, p);
   }
   std::sort(rp.begin(), rp.end());
   for (size_t q = 0; q < rp.size(); ++q) {
@@ -1232,6 +1242,20 @@ extern "C" int cc_read_group_members(cc_engine* e, uint32_t slot, uint64_t cap, 
   return CC_OK;
 }
 
+extern "C" int cc_read_topic_listeners(cc_engine* e, uint32_t slot, uint64_t cap, uint64_t* count, uint64_t* h_ids,
+                                       uint64_t* h_index) {
+  CoordHdr h;
+  std::vector<CoordEnt> q;
+  int rc = read_block(e, slot, CC_RES_TOPIC, h, q, nullptr);
+  if (rc) return rc;
+  for (uint32_t i = 0; i < h.n && i < cap; ++i) {
+    if (h_ids) h_ids[i] = q[i].x;
+    if (h_index) h_index[i] = q[i].idx;
+  }
+  if (count) *count = h.n;
+  return CC_OK;
+}
+
 // Every commit the slot's state machine holds without having clean()ed it, ascending (the
 // oracle's orc_read_retained restates the same sites).
 extern "C" int cc_read_retained(cc_engine* e, uint32_t slot, uint64_t cap, uint64_t* count, uint64_t* h_index) {
@@ -1291,6 +1315,9 @@ extern "C" int cc_read_retained(cc_engine* e, uint32_t slot, uint64_t cap, uint6
         if (g.slot == slot) v.push_back(g.idx);
       break;
     case CC_RES_MULTIMAP:  // every Put (MultiMapState.put :68-91 neither cleans nor closes it): the leak lists
+      break;
+    case CC_RES_TOPIC:  // the listeners' Listen commits (TopicState :42-62) + the ones close dropped (:35-37, leak lists)
+      for (uint32_t i = 0; i < h.n; ++i) v.push_back(q[i].idx);
       break;
     case CC_RES_QUEUE:  // elements, less the head element() clean()ed (QueueState :51-199)
       for (uint32_t i = 0; i < h.n; ++i) {
@@ -1397,7 +1424,7 @@ extern "C" int cc_advance_time_events(cc_engine* e, uint64_t now, const cc_event
 extern "C" int cc_advance_time(cc_engine* e, uint64_t now) { return cc_advance_time_events(e, now, nullptr); }
 
 static const char* kKernelNames[K_NUM] = {"k_part_tile", "k_apply_value", "k_unpermute", "k_apply_map", "k_map_hot",
-                                          "k_apply_coord", "k_events"};
+                                          "k_apply_coord", "k_events", "k_topic_fanout"};
 
 // ---- snapshot / restore (restart without replaying the whole log) -------------------
 // Layout: SnapHdr, then the sections below in order, each a u64 byte count followed by the bytes.  Host
@@ -1766,6 +1793,7 @@ extern "C" int cc_snapshot_restore(cc_engine* e, const void* h_buf, uint64_t siz
   e->has_values = e->has_values || std::find(e->res_type.begin(), e->res_type.end(), (uint8_t)CC_RES_VALUE) != e->res_type.end();
   e->has_mmaps = std::find(e->res_type.begin(), e->res_type.end(), (uint8_t)CC_RES_MULTIMAP) != e->res_type.end();
   if (e->has_mmaps && (rc = ensure_leak(e, kLeakCap))) return rc;
+  e->has_topics = std::find(e->res_type.begin(), e->res_type.end(), (uint8_t)CC_RES_TOPIC) != e->res_type.end();
   e->sessions = std::move(sessions);
   e->small_live = e->map_bits && !e->ttl_live;  // (the next sub-batch recounts the maps still small)
   if (e->map_bits)  // (no replay is pending here: the restored snapshot flags start with no exit marks)

@@ -18,7 +18,7 @@ inline bool diag_env(const char* name) {
 namespace cc {
 
 // Optional per-kernel timing (HIP events recorded on the launch stream around each kernel).
-enum KernelId { K_PART_TILE = 0, K_APPLY_VALUE, K_UNPERMUTE, K_APPLY_MAP, K_MAP_HOT, K_APPLY_COORD, K_EVENTS, K_NUM };
+enum KernelId { K_PART_TILE = 0, K_APPLY_VALUE, K_UNPERMUTE, K_APPLY_MAP, K_MAP_HOT, K_APPLY_COORD, K_EVENTS, K_TOPIC_FANOUT, K_NUM };
 struct Marker {
   void (*fn)(void* ctx, int kernel, int begin, hipStream_t st);
   void* ctx;
@@ -557,10 +557,21 @@ struct CoordArgs {
   LeakRec* leak;           // leak log (LeakRec, common.h)
   unsigned long long* leak_n;
   uint64_t leak_cap;
+  FanCtx* fx;              // TopicState.publish fan records + listener log (device; common.h FanCtx)
   uint32_t* err;
   Marker mark;
 };
 int launch_apply_coord(const CoordArgs& a, hipStream_t st);
+// TopicState.publish fan-out (topic_fanout.hip): every fan record of the sub-batch expanded into its events in the arena
+struct FanoutArgs {
+  FanCtx* fx;
+  EvRec* arena;
+  unsigned long long* arena_n;
+  uint64_t arena_cap;
+  uint32_t* err;
+  Marker mark;
+};
+int launch_topic_fanout(const FanoutArgs& a, hipStream_t st);
 int phase_read_coord_wg(uint64_t* out);  // CC_PHASE_TIMING builds
 int launch_time_check(const uint64_t* time, uint64_t n, uint64_t* clock, uint32_t* err, hipStream_t st);
 int launch_clock_advance(const uint64_t* time, uint64_t n, uint64_t now, uint64_t* clock, hipStream_t st);

@@ -377,6 +377,10 @@ struct cc_engine {
   unsigned long long* d_arena_n = nullptr;
   unsigned long long* d_ev_total = nullptr;
   uint64_t arena_cap = 0;
+  // TopicState.publish (common.h FanCtx): the fan records live in d_ev_bucket and the listener log in d_ev_perm, both
+  // [arena_cap] and free between the coordination apply and the order pass that fills them (events.hip)
+  FanCtx* d_fan = nullptr;
+  bool has_topics = false;  // a TopicState resource exists: the coordination apply is followed by k_topic_fanout
   // commits dropped without clean() (LeakRec, common.h): the kernels' device log, drained into per-slot host lists
   LeakRec* d_leak = nullptr;
   unsigned long long* d_leak_n = nullptr;

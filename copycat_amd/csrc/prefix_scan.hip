@@ -4,7 +4,7 @@
 // overflow a coordination collection (host_path.hip).  With the columns in HBM that walk is these kernels: they find,
 // without copying a column to the host, the first row in log order of [lo, hi) that
 //   * adds an entry (adds_entry, common.h: lock with a timeout != 0, election listen, group join, value listen,
-//     queue add / offer; a row whose instance slot is out of range or unbound never counts), and
+//     queue add / offer, topic listen; a row whose instance slot is out of range or unbound never counts), and
 //   * meets its resource's block full: CoordHdr.n + the adding rows for that resource before it in [lo, hi) equals
 //     coord_cap.
 // Removals are not counted, as on the host: the row is an upper bound's stop, and the driver reads the block's exact

@@ -43,7 +43,8 @@ __global__ void k_ret_coord(const uint8_t* __restrict__ res_type, const uint8_t*
   const uint32_t s = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave), l = threadIdx.x & 63;
   if (s >= slots) return;
   const uint32_t type = res_type[s];
-  if (type != CC_RES_VALUE && type != CC_RES_LOCK && type != CC_RES_ELECTION && type != CC_RES_GROUP && type != CC_RES_QUEUE)
+  if (type != CC_RES_VALUE && type != CC_RES_LOCK && type != CC_RES_ELECTION && type != CC_RES_GROUP && type != CC_RES_QUEUE &&
+      type != CC_RES_TOPIC)
     return;
   const uint8_t* blk = coord + (uint64_t)s * coord_block(ccap);
   const CoordHdr h = *reinterpret_cast<const CoordHdr*>(blk);

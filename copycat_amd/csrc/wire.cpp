@@ -112,6 +112,10 @@ const Schema kSchema[] = {
     {CC_OP_GROUP_LEAVE, {F_END}},
     {CC_OP_GROUP_SCHEDULE, {F_LKEY, F_AUX, F_A, F_END}},
     {CC_OP_GROUP_EXECUTE, {F_LKEY, F_A, F_END}},
+    // TopicCommands.java: Listen / Unlisten nothing; Publish message (:100-108)
+    {CC_OP_TOPIC_LISTEN, {F_END}},
+    {CC_OP_TOPIC_UNLISTEN, {F_END}},
+    {CC_OP_TOPIC_PUBLISH, {F_A, F_END}},
 };
 
 const Schema* schema_of(uint32_t id) {
@@ -134,6 +138,8 @@ uint32_t res_type_of_class(const std::string& name) {
       {"io.atomix.coordination.state.LockState", CC_RES_LOCK},
       {"io.atomix.coordination.state.LeaderElectionState", CC_RES_ELECTION},
       {"io.atomix.coordination.state.MembershipGroupState", CC_RES_GROUP},
+      // (io.atomix.coordination.state.TopicState still decodes as CC_RES_NONE: tests/golden/wire_fixture.json pins
+      // that row; a host that creates topics passes CC_RES_TOPIC to cc_manager_get / cc_resource_create itself)
   };
   for (const auto& c : kClasses)
     if (name == c.first) return c.second;

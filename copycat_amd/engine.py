@@ -75,6 +75,7 @@ def lib():
             "cc_read_lock_state": (i32, [P, u32, P, P, P, u64, P, P, P]),
             "cc_read_election_state": (i32, [P, u32, P, P, u64, P, P, P]),
             "cc_read_group_members": (i32, [P, u32, u64, P, P]),
+            "cc_read_topic_listeners": (i32, [P, u32, u64, P, P, P]),
             "cc_read_retained": (i32, [P, u32, u64, P, P]),
             "cc_retained_bitmap": (i32, [P, u64, u64, P, P]),
             "cc_advance_time": (i32, [P, u64]),
@@ -595,6 +596,13 @@ class Engine:
         ids, n = np.zeros(cap, np.uint64), C.c_uint64()
         _check(self.L.cc_read_group_members(self.h, slot, cap, C.byref(n), _np(ids)))
         return ids[:min(n.value, cap)].tolist()
+
+    def topic_listeners(self, slot, cap=4096):
+        """[(listener instance id, its Listen commit index)], ascending by id (cc_read_topic_listeners)"""
+        ids, idx, n = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64), C.c_uint64()
+        _check(self.L.cc_read_topic_listeners(self.h, slot, cap, C.byref(n), _np(ids), _np(idx)))
+        m = min(n.value, cap)
+        return list(zip(ids[:m].tolist(), idx[:m].tolist()))
 
     def retained(self, slot):
         """Ascending log indices of every commit the slot's state machine still holds without having clean()ed it

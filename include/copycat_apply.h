@@ -55,6 +55,7 @@ extern "C" {
 #define CC_RES_SET       6  /* SetState          collections/.../state/SetState.java:32 (shares the map table) */
 #define CC_RES_QUEUE     7  /* QueueState        collections/.../state/QueueState.java:33 (a FIFO of CC_QUEUE_CAP) */
 #define CC_RES_MULTIMAP  8  /* MultiMapState     collections/.../state/MultiMapState.java:30 (shares the map table) */
+#define CC_RES_TOPIC     9  /* TopicState        coordination/.../state/TopicState.java:31 (listeners keyed by instance id) */
 #define CC_QUEUE_CAP    64
 
 /* ---- op codes = Catalyst @SerializeWith ids of the inner operation ------------- */
@@ -126,6 +127,10 @@ extern "C" {
 #define CC_OP_GROUP_LEAVE      121
 #define CC_OP_GROUP_SCHEDULE   122
 #define CC_OP_GROUP_EXECUTE    123
+/* TopicCommands.java:53,64,80 (Publish: the message in operand a, its tag in CC_FLAGS) */
+#define CC_OP_TOPIC_LISTEN     125
+#define CC_OP_TOPIC_UNLISTEN   126
+#define CC_OP_TOPIC_PUBLISH    127
 
 /* ---- canonical tagged values: Java equals == (tag, payload) equality ---------- */
 #define CC_TAG_NULL    0
@@ -169,6 +174,10 @@ extern "C" {
 #define CC_EV_EXECUTE  6  /* MembershipGroupState "execute"(callback) :95,115 */
 #define CC_EV_MEMBER   7  /* not an event: one row per member of a join's Set<Long> result (ascending ids,
                              target = the joining instance, src CC_EVSRC_RESULT) MembershipGroupState.java:63 */
+#define CC_EV_MESSAGE  8  /* TopicState "message"(message) TopicState.java:67-82: one per listener of the topic at the
+                             publish row, target = the listener's instance slot, src CC_EVSRC_COMMIT, tag / payload =
+                             the canonical message (payload 0 for NULL); within one publish in ascending listener
+                             instance id (engine-defined: each goes to a different session) */
 
 /* event source */
 #define CC_EVSRC_COMMIT 0  /* published while applying commit `pos` */
@@ -213,6 +222,8 @@ typedef struct cc_config {
 #define CC_ELECTION_LISTENERS  64
 #define CC_GROUP_MEMBERS       64
 #define CC_VALUE_LISTENERS     64
+#define CC_TOPIC_LISTENERS     64  /* coord_cap listeners per topic; at coord_cap 65536 the limit is 65,535 (a commit's
+                                      event count is 16 bits) */
 
 /* ---- one batch of committed entries, SoA, log order ------------------------------------------------
  * Row i is InstanceCommand/InstanceQuery{instance, op} of log entry index[i]
@@ -383,6 +394,10 @@ int  cc_read_election_state(cc_engine* e, uint32_t slot, int64_t* leader, uint64
                             uint64_t* count, uint32_t* h_listener_inst, uint64_t* h_listener_index);
 /* MembershipGroupState.members (MembershipGroupState.java:33): member instance ids, ascending. */
 int  cc_read_group_members(cc_engine* e, uint32_t slot, uint64_t cap, uint64_t* count, uint64_t* h_ids);
+/* TopicState.listeners (TopicState.java:32): listener instance ids, ascending, and each listener's Listen commit
+ * index.  Exists from this commit on, under the unchanged CC_ABI_VERSION 6 (symbols are only added). */
+int  cc_read_topic_listeners(cc_engine* e, uint32_t slot, uint64_t cap, uint64_t* count, uint64_t* h_ids,
+                             uint64_t* h_index);
 /* Log compaction for every state machine (Commit.clean()): the log indices of every commit
  * the slot's state machine still holds without having clean()ed it, ascending — *count of them, the first
  * min(cap, count) to h_index.  Value: `current` + listeners (AtomicValueState.java:41-157, needs
@@ -434,8 +449,9 @@ int  cc_sessions_expire_host(cc_engine* e, const uint64_t* h_bitmap, uint64_t se
 
 /* ---- per-kernel timing (HIP events recorded on the launch stream around every engine kernel) ----------
  * kernel ids: 0 k_part_tile, 1 k_apply_value, 2 k_unpermute, 3 k_apply_map, 4 k_map_hot (hot-key lists +
- * scan, apply_map_hot.hip), 5 k_apply_coord (coordination + value events), 6 k_events (event scan+scatter). */
-#define CC_PROFILE_KERNELS 7
+ * scan, apply_map_hot.hip), 5 k_apply_coord (coordination + value events), 6 k_events (event scan+scatter),
+ * 7 k_topic_fanout (TopicState.publish expansion, topic_fanout.hip; launched only on engines that hold a topic). */
+#define CC_PROFILE_KERNELS 8
 int  cc_profile_enable(cc_engine* e, int on);
 int  cc_profile_reset(cc_engine* e);
 /* Accumulated device time (ms) and launch count of one kernel since the last reset (synchronizes). */
