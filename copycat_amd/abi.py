@@ -298,6 +298,18 @@ class cc_respack_block(C.Structure):
     _fields_ = [("rows", C.c_uint32), ("bytes", C.c_uint32), ("offset", C.c_uint64), ("col", cc_pack_col * 2)]
 
 
+# packed event blobs (include/copycat_apply.h "packed event blobs"; copycat_amd/csrc/evpack.cpp, evpack.hip)
+CC_EVPACK_MAGIC = 1162888003
+CC_EVPACK_VERSION = 1
+CC_EVPACK_COLUMNS = 6
+CC_PK_BY_POS = 2
+EVENT_COLUMNS = (("pos", "u4"), ("target", "u4"), ("code", "u1"), ("src", "u1"), ("tag", "u1"), ("payload", "u8"))  # col order
+
+
+class cc_evpack_block(C.Structure):
+    _fields_ = [("rows", C.c_uint32), ("bytes", C.c_uint32), ("offset", C.c_uint64), ("col", cc_pack_col * 6)]
+
+
 class cc_packed_opts(C.Structure):
     _fields_ = [
         ("chunk_rows", C.c_uint64),

@@ -230,6 +230,91 @@ def results_info(blob):
     return {"n": n, "blocks": hd.blocks, "bytes": hd.bytes, "bytes_per_row": hd.bytes / n if n else 0.0, "columns": cols}
 
 
+def events_bound(n):
+    """cc_evpack_bound: the worst-case size of a packed event blob of n events."""
+    import ctypes as C
+
+    bound = C.c_uint64()
+    rc = _pack_lib().cc_evpack_bound(n, C.byref(bound))
+    if rc:
+        _pack_fail(rc)
+    return bound.value
+
+
+def pack_events(events, threads=0, out=None):
+    """cc_evpack_pack, the host reference encoder: event columns ({"pos", "target", "code", "src", "tag", "payload"}, as
+    apply_host_events returns them) as one packed event blob, a 16-byte-aligned uint8 array.  `out`: a 16-byte-aligned
+    uint8 buffer to pack into; the result is a view of it."""
+    import ctypes as C
+
+    cols = []
+    for name, dt in abi.EVENT_COLUMNS:
+        a = np.ascontiguousarray(events[name])
+        a = a.view(np.dtype(dt)) if a.dtype.kind == "i" and a.dtype.itemsize == np.dtype(dt).itemsize else a
+        cols.append(np.ascontiguousarray(a, dtype=np.dtype(dt)))
+    n = len(cols[0])
+    if any(len(c) != n for c in cols):
+        raise ValueError("event columns differ in length")
+    blob = out if out is not None else _aligned_bytes(events_bound(n))
+    ev = abi.cc_events(*(c.ctypes.data for c in cols), n, None)
+    size = C.c_uint64()
+    rc = _pack_lib().cc_evpack_pack(C.byref(ev), n, blob.ctypes.data, blob.nbytes, threads, C.byref(size))
+    if rc:
+        _pack_fail(rc)
+    return blob[:size.value]
+
+
+def events_check(blob):
+    """cc_evpack_check: the events of a well-formed event blob; raises EngineError (CC_ERR_INVALID) otherwise."""
+    import ctypes as C
+
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    n = C.c_uint64()
+    rc = _pack_lib().cc_evpack_check(blob.ctypes.data, blob.nbytes, C.byref(n))
+    if rc:
+        _pack_fail(rc)
+    return n.value
+
+
+def unpack_events(blob, threads=0):
+    """cc_evpack_unpack, the host decoder: the six numpy columns of a packed event blob, as a dict."""
+    import ctypes as C
+
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    n = events_check(blob)
+    cols = {name: np.zeros(n, np.dtype(dt)) for name, dt in abi.EVENT_COLUMNS}
+    count = np.zeros(1, np.uint64)
+    ev = abi.cc_events(*(cols[name].ctypes.data for name, _ in abi.EVENT_COLUMNS), n, count.ctypes.data)
+    rc = _pack_lib().cc_evpack_unpack(blob.ctypes.data, blob.nbytes, C.byref(ev), threads)
+    if rc:
+        _pack_fail(rc)
+    return cols
+
+
+def events_info(blob):
+    """The directory of a packed event blob, as pack_info: {"n", "blocks", "bytes", "bytes_per_row", "columns": {name:
+    {"rows": {(mode, width): rows}, "bytes_per_row", "blocks": [(mode, width, base, entries), ...]}}}; `entries` is a
+    CC_PK_BY_POS table's entry count (0 in mode CC_PK_FOR)."""
+    import ctypes as C
+
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    n = events_check(blob)
+    hd = abi.cc_pack_header.from_buffer_copy(blob[:C.sizeof(abi.cc_pack_header)].tobytes())
+    lo = C.sizeof(abi.cc_pack_header)
+    dir_ = (abi.cc_evpack_block * hd.blocks).from_buffer_copy(
+        blob[lo:lo + hd.blocks * C.sizeof(abi.cc_evpack_block)].tobytes())
+    cols = {}
+    for c, (name, _) in enumerate(abi.EVENT_COLUMNS):
+        rows, blocks, size = {}, [], 0
+        for blk in dir_:
+            e = blk.col[c]
+            rows[(e.mode, e.width)] = rows.get((e.mode, e.width), 0) + blk.rows
+            blocks.append((e.mode, e.width, e.base, e.reserved16))
+            size += (e.reserved16 if e.mode == abi.CC_PK_BY_POS else blk.rows) * e.width
+        cols[name] = {"rows": rows, "blocks": blocks, "bytes_per_row": size / n if n else 0.0}
+    return {"n": n, "blocks": hd.blocks, "bytes": hd.bytes, "bytes_per_row": hd.bytes / n if n else 0.0, "columns": cols}
+
+
 def tagged(v):
     """Python value -> canonical (tag, payload).  None -> NULL; bool -> BOOL; int -> LONG.
 

@@ -123,6 +123,9 @@ static void free_all(cc_engine* e) {
   for (hipEvent_t ev : e->pk_stamp) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->rp_stamp) (void)hipEventDestroy(ev);
   if (e->rp_pin) (void)hipHostFree(e->rp_pin);
+  for (hipEvent_t ev : e->ep_stamp) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : e->ep_call_stamp) (void)hipEventDestroy(ev);
+  if (e->ep_pin) (void)hipHostFree(e->ep_pin);
   for (hipStream_t s : {e->pk_in, e->pk_out})
     if (s) (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s);
   if (e->side_st) (void)hipStreamDestroy(e->side_st);

@@ -764,4 +764,22 @@ struct RespackArgs {
 constexpr uint32_t kRespackPlacePass = 256;  // blocks one pass of the placement scan holds (one per lane)
 int launch_respack(const RespackArgs& a, hipStream_t st);
 
+// Wide event columns -> the directory and data areas of an event blob (evpack.hip): block k of `dir` encodes events
+// [4096 k, ...) of the six columns (each 16-byte aligned).  `data` takes the blob's bytes from blob offset `data_base`
+// (a multiple of 16) on, with room for the worst case (19 bytes per event + 96); *total = the data bytes written.
+struct EvpackArgs {
+  const uint32_t* pos;
+  const uint32_t* target;
+  const uint8_t* code;
+  const uint8_t* src;
+  const uint8_t* tag;
+  const uint64_t* payload;
+  uint64_t n;
+  cc_evpack_block* dir;
+  uint8_t* data;
+  uint64_t data_base;
+  unsigned long long* total;
+};
+int launch_evpack(const EvpackArgs& a, hipStream_t st);
+
 }  // namespace cc

@@ -423,6 +423,12 @@ struct cc_engine {
   std::vector<hipEvent_t> rp_stamp;  // 10 per chunk of the last call: H2D, decode, apply, encode, D2H begin / end
   uint64_t rp_chunks = 0;
   uint64_t* rp_pin = nullptr;
+  // cc_apply_batch_host_packed_events: its stamps (10 per chunk as above, then 4 per call: event encode and event D2H
+  // begin / end), and the pinned host words a chunk's event count and the event encoder's total are read back into
+  // (also cc_evpack_from_device's)
+  std::vector<hipEvent_t> ep_stamp, ep_call_stamp;
+  uint64_t ep_chunks = 0;
+  uint64_t* ep_pin = nullptr;
   // per-kernel profiling (cc_profile_enable)
   bool prof_on = false;
   std::vector<hipEvent_t> ev_pool;

@@ -14,6 +14,7 @@
 // (cc_quorum_commit, cc_expire_sweep) and for hosts that keep columns resident.
 #include <algorithm>
 #include <cstring>
+#include <string>
 
 #include <unordered_map>
 
@@ -1225,6 +1226,359 @@ extern "C" int cc_packed_results_timeline(cc_engine* e, uint64_t cap, uint64_t* 
   for (uint64_t k = 0; k < std::min(cap, e->rp_chunks); ++k)
     for (int j = 0; j < 5; ++j)
       HIPCHECK(hipEventElapsedTime(h_ms + 5 * k + j, e->rp_stamp[10 * k + 2 * j], e->rp_stamp[10 * k + 2 * j + 1]));
+  return CC_OK;
+}
+
+// ---- packed event blobs (evpack.cpp, evpack.hip) ----------------------------------------------------------------------
+// cc_apply_batch_host_packed_events is cc_apply_batch_host_packed_results with the event stream kept in HBM:
+//
+//   copy-in  (pk_in)      | H2D 0 | H2D 1 |      H2D 2      |
+//   engine   (own_stream)         | dec 0 + apply 0 + enc 0 + shift 0 | dec 1 + apply 1 + enc 1 + shift 1 | ... | ev enc | ev D2H |
+//   copy-out (pk_out)                                       | D2H 0 |                             | D2H 1 |
+//
+// Chunk k's events are appended to engine-owned device columns after those of the chunks before (cc_apply_batch
+// writes them there), its count comes back in a pinned word with the chunk's checks, and its pos values are shifted to
+// batch rows by a kernel.  The blob is encoded once, after the last chunk, and leaves in one D2H: the directory's
+// length, and with it the offset of every data area, is known only with the last chunk's count, so a block sent earlier
+// would have no final place in the caller's blob (the result blob knows its row count up front).  The body follows
+// cc_apply_batch_host_packed_results stage by stage; that call is left as it was (the baseline this one is measured
+// against).
+namespace {
+
+enum EpSlot : int { kHwEvAcc = kRpSlots, kHwEvStage, kEpSlots };
+static_assert(kEpSlots <= 32, "cc_engine::hw_buf");
+constexpr uint64_t kEpHead = 16;  // the first bytes of both buffers: the count word / the encoder's total word
+
+uint64_t ep_r16(uint64_t x) { return (x + 15) & ~15ull; }
+
+// engine-owned device event columns of `cap` events, each 16-byte aligned, in one allocation behind the count word
+int ep_columns(cc_engine* e, uint64_t cap, cc_events* d) {
+  const uint64_t c = std::max<uint64_t>(cap, 1);
+  void* p = nullptr;
+  TRY(hw(e, kHwEvAcc, kEpHead + ep_r16(8 * c) + 2 * ep_r16(4 * c) + 3 * ep_r16(c), &p));
+  uint8_t* q = (uint8_t*)p;
+  d->count = (uint64_t*)q, q += kEpHead;
+  d->payload = (uint64_t*)q, q += ep_r16(8 * c);
+  d->pos = (uint32_t*)q, q += ep_r16(4 * c);
+  d->target = (uint32_t*)q, q += ep_r16(4 * c);
+  d->code = q, q += ep_r16(c);
+  d->src = q, q += ep_r16(c);
+  d->tag = q;
+  d->capacity = cap;
+  return CC_OK;
+}
+
+void ep_header(void* h_blob, uint64_t n, uint64_t bytes) {
+  cc_pack_header hd{};
+  hd.magic = (uint32_t)CC_EVPACK_MAGIC;
+  hd.version = CC_EVPACK_VERSION;
+  hd.n = n;
+  hd.blocks = rp_blocks(n);
+  hd.bytes = bytes;
+  hd.present = 0x3F;
+  hd.block_rows = CC_PACK_BLOCK_ROWS;
+  std::memcpy(h_blob, &hd, sizeof hd);
+}
+
+int ep_pin(cc_engine* e) {
+  if (!e->ep_pin) HIPCHECK(hipHostMalloc((void**)&e->ep_pin, 16, hipHostMallocDefault));
+  return CC_OK;
+}
+
+// the first m events of the device columns `d` (each 16-byte aligned) as an event blob in h_blob: encoded in the
+// engine's staging on `st`, then header + directory + the data bytes used copied out.  Synchronous.  stamp: four HIP
+// events (encode begin / end, D2H begin / end) or null.
+int ep_encode(cc_engine* e, const cc_events* d, uint64_t m, void* h_blob, hipStream_t st, uint64_t* bytes,
+              const hipEvent_t* stamp) {
+  auto mark = [&](int i) { return stamp ? hipEventRecord(stamp[i], st) : hipSuccess; };
+  const uint64_t db = rp_blocks(m) * sizeof(cc_evpack_block);
+  *bytes = sizeof(cc_pack_header);
+  HIPCHECK(mark(0));
+  uint8_t* p = nullptr;
+  if (m) {
+    if (rp_blocks(m) > 0x7FFFFFFFull) return set_err(CC_ERR_CAPACITY, "event blob: more than 2^31 blocks");
+    TRY(ep_pin(e));
+    void* v = nullptr;
+    TRY(hw(e, kHwEvStage, kEpHead + db + 19 * m + 96, &v));  // (every column raw; the tail block's six paddings)
+    p = (uint8_t*)v;
+    EvpackArgs a{};
+    a.pos = d->pos, a.target = d->target, a.code = d->code, a.src = d->src, a.tag = d->tag, a.payload = d->payload;
+    a.n = m;
+    a.dir = (cc_evpack_block*)(p + kEpHead);
+    a.data = p + kEpHead + db;
+    a.data_base = sizeof(cc_pack_header) + db;
+    a.total = (unsigned long long*)p;
+    if (launch_evpack(a, st)) return set_err(CC_ERR_HIP, "event blob encode launch", hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(e->ep_pin + 1, p, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHECK(mark(1));
+  HIPCHECK(hipStreamSynchronize(st));
+  HIPCHECK(mark(2));
+  if (m) {
+    const uint64_t total = e->ep_pin[1];
+    if (total > 19 * m + 96) return set_err(CC_ERR_STATE, "internal check: the event blob encoder wrote past its bound");
+    // directory and data are adjacent in the staging as they are in the blob: one copy
+    HIPCHECK(hipMemcpyAsync((uint8_t*)h_blob + sizeof(cc_pack_header), p + kEpHead, db + total, hipMemcpyDeviceToHost, st));
+    *bytes += db + total;
+  }
+  HIPCHECK(mark(3));
+  HIPCHECK(hipStreamSynchronize(st));
+  ep_header(h_blob, m, *bytes);
+  return CC_OK;
+}
+
+}  // namespace
+
+extern "C" int cc_evpack_from_device(cc_engine* e, const cc_events* d, void* h_blob, uint64_t cap_bytes, uint64_t* bytes,
+                                     uint64_t* count, void* stream) {
+  if (!e || !d || !bytes || !h_blob || !d->count) return set_err(CC_ERR_INVALID, "event blob: null argument");
+  if ((uintptr_t)h_blob & 15) return set_err(CC_ERR_INVALID, "event blob: the blob must be 16-byte aligned");
+  uint64_t bound = 0;
+  TRY(cc_evpack_bound(d->capacity, &bound));
+  if (cap_bytes < bound) {
+    *bytes = bound;
+    return set_err(CC_ERR_CAPACITY, "event blob: the blob buffer is smaller than cc_evpack_bound (*bytes = the bound)");
+  }
+  HIPCHECK(hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  uint64_t cnt = 0;
+  HIPCHECK(hipMemcpyAsync(&cnt, d->count, sizeof cnt, hipMemcpyDeviceToHost, st));
+  HIPCHECK(hipStreamSynchronize(st));  // (the stream is drained: the columns and the count are final)
+  if (count) *count = cnt;
+  const uint64_t m = std::min(cnt, d->capacity);
+  if (m && (!d->pos || !d->target || !d->code || !d->src || !d->tag || !d->payload ||
+            (((uintptr_t)d->pos | (uintptr_t)d->target | (uintptr_t)d->code | (uintptr_t)d->src | (uintptr_t)d->tag |
+              (uintptr_t)d->payload) & 15)))
+    return set_err(CC_ERR_INVALID, "event blob: the six device columns must be non-null and 16-byte aligned");
+  TRY(ep_encode(e, d, m, h_blob, st, bytes, nullptr));
+  if (cnt > d->capacity) return set_err(CC_ERR_CAPACITY, "more events than the event stream holds");
+  return CC_OK;
+}
+
+extern "C" int cc_apply_batch_host_packed_events(cc_engine* e, const void* h_blob, uint64_t bytes, void* h_res_blob,
+                                                 uint64_t res_cap, uint64_t* res_bytes, void* h_ev_blob,
+                                                 uint64_t ev_capacity, uint64_t ev_cap_bytes, uint64_t* ev_bytes,
+                                                 uint64_t* ev_count, const cc_packed_opts* opts, uint64_t* h_rows_done) {
+  if (h_rows_done) *h_rows_done = 0;
+  if (!e || !h_res_blob || !res_bytes) return set_err(CC_ERR_INVALID, "result blob: null argument");
+  if ((uintptr_t)h_res_blob & 15) return set_err(CC_ERR_INVALID, "result blob: the blob must be 16-byte aligned");
+  if (!h_ev_blob || !ev_bytes || !ev_count) return set_err(CC_ERR_INVALID, "event blob: null argument");
+  if ((uintptr_t)h_ev_blob & 15) return set_err(CC_ERR_INVALID, "event blob: the blob must be 16-byte aligned");
+  if (opts && (opts->flags & ~(uint32_t)CC_PACKED_TIMELINE)) return set_err(CC_ERR_INVALID, "packed apply: unknown flag");
+  uint64_t n = 0;
+  uint32_t present = 0;
+  TRY(cc_pack_check(h_blob, bytes, &n, &present));  // (before anything is copied or launched)
+  uint64_t bound = 0;
+  TRY(cc_respack_bound(n, &bound));
+  if (res_cap < bound) {
+    *res_bytes = bound;
+    return set_err(CC_ERR_CAPACITY, "result blob: the blob buffer is smaller than cc_respack_bound (*res_bytes = the bound)");
+  }
+  TRY(cc_evpack_bound(ev_capacity, &bound));
+  if (ev_cap_bytes < bound) {
+    *ev_bytes = bound;
+    return set_err(CC_ERR_CAPACITY, "event blob: the blob buffer is smaller than cc_evpack_bound (*ev_bytes = the bound)");
+  }
+  if (n && (present & kPkNeed) != kPkNeed)
+    return set_err(CC_ERR_INVALID, "inst/op/flags/a/b columns and status/value outputs are required");
+  // from here on every return leaves a valid result blob of the rows copied out so far and a valid event blob
+  rp_header(h_res_blob, 0, sizeof(cc_pack_header));
+  *res_bytes = sizeof(cc_pack_header);
+  ep_header(h_ev_blob, 0, sizeof(cc_pack_header));
+  *ev_bytes = sizeof(cc_pack_header);
+  *ev_count = 0;
+  HIPCHECK(hipSetDevice(e->device));
+  e->ep_chunks = 0;
+  if (n == 0) return CC_OK;
+  e->last_err_bits = 0;
+  hipStream_t st = e->own_stream;
+  if (st != e->last_stream) HIPCHECK(hipStreamSynchronize(e->last_stream));
+  e->last_stream = st;
+  TRY(pk_init(e));
+  TRY(ep_pin(e));
+
+  const uint64_t kB = CC_PACK_BLOCK_ROWS;
+  uint64_t chunk = opts && opts->chunk_rows ? opts->chunk_rows : (16ull << 20);
+  chunk = std::min<uint64_t>(chunk, 1ull << 40);
+  chunk = (chunk + kB - 1) / kB * kB;
+  const uint64_t cap_rows = std::max<uint64_t>(std::min(e->cfg.max_batch, e->sub_ext) / kB * kB, kB);
+  chunk = std::min(chunk, cap_rows);
+  const uint64_t bpc = chunk / kB, nchunks = (n + chunk - 1) / chunk;
+  TRY(ckpt_reserve(e));  // (an event stream: every chunk runs under a device checkpoint)
+  const bool stamps = opts && (opts->flags & CC_PACKED_TIMELINE);
+  if (stamps) {
+    while (e->ep_stamp.size() < 10 * nchunks) {
+      hipEvent_t ev;
+      HIPCHECK(hipEventCreate(&ev));
+      e->ep_stamp.push_back(ev);
+    }
+    while (e->ep_call_stamp.size() < 4) {
+      hipEvent_t ev;
+      HIPCHECK(hipEventCreate(&ev));
+      e->ep_call_stamp.push_back(ev);
+    }
+  }
+  auto stamp = [&](uint64_t k, int which, hipStream_t s) -> hipError_t {
+    return stamps ? hipEventRecord(e->ep_stamp[10 * k + which], s) : hipSuccess;
+  };
+  cc_events acc{};  // the call's events, in HBM
+  TRY(ep_columns(e, ev_capacity, &acc));
+
+  const cc_pack_header* hd = (const cc_pack_header*)h_blob;
+  const uint8_t* const blob = (const uint8_t*)h_blob;
+  const cc_pack_block* const dir = (const cc_pack_block*)(blob + sizeof *hd);
+  void* piece[2] = {};
+  uint64_t piece_base[2] = {}, piece_dir[2] = {};
+  // chunk k's piece on its way: directory entries, then the data areas of its blocks
+  auto send = [&](uint64_t k) -> int {
+    const uint64_t b0 = k * bpc, b1 = std::min(hd->blocks, b0 + bpc);
+    const uint64_t lo = dir[b0].offset, hi = dir[b1 - 1].offset + dir[b1 - 1].bytes, db = (b1 - b0) * sizeof(cc_pack_block);
+    void* p = nullptr;
+    TRY(hw(e, kHwBlob0 + (int)(k & 1), db + (hi - lo), &p));
+    HIPCHECK(stamp(k, 0, e->pk_in));
+    HIPCHECK(hipMemcpyAsync(p, dir + b0, db, hipMemcpyHostToDevice, e->pk_in));
+    if (hi > lo) HIPCHECK(hipMemcpyAsync((uint8_t*)p + db, blob + lo, hi - lo, hipMemcpyHostToDevice, e->pk_in));
+    HIPCHECK(stamp(k, 1, e->pk_in));
+    HIPCHECK(hipEventRecord(e->pk_landed[k & 1], e->pk_in));
+    piece[k & 1] = p, piece_base[k & 1] = lo, piece_dir[k & 1] = db;
+    return CC_OK;
+  };
+  uint8_t* const res = (uint8_t*)h_res_blob;
+  const uint64_t res_data0 = sizeof(cc_pack_header) + rp_blocks(n) * sizeof(cc_respack_block);
+  uint64_t res_rows = 0, res_data = 0;  // rows whose results are on their way out, and their data bytes
+  uint64_t ev_n = 0;                    // events of the chunks so far (the failing chunk's included)
+  uint64_t ev_kept = 0;                 // events of the chunks fully applied: the blob's
+  // every stream drained before the call returns; the event blob is encoded and sent here, the headers go last
+  auto leave = [&](int rc) {
+    (void)hipStreamSynchronize(e->pk_in);
+    (void)hipStreamSynchronize(e->pk_out);
+    *ev_count = ev_n;
+    *res_bytes = res_rows ? res_data0 + res_data : sizeof(cc_pack_header);
+    rp_header(res, res_rows, *res_bytes);
+    const char* const why = rc ? cc_last_error() : nullptr;
+    const std::string kept = why ? why : "";
+    const int re = ep_encode(e, &acc, ev_kept, h_ev_blob, st, ev_bytes, stamps ? e->ep_call_stamp.data() : nullptr);
+    if (re) {  // (the header-only blob written above stands)
+      *ev_bytes = sizeof(cc_pack_header);
+      if (rc) (void)set_err(rc, kept.c_str());
+    }
+    return rc ? rc : re;
+  };
+  int rc = send(0);
+  if (rc) return leave(rc);
+  for (uint64_t k = 0; k < nchunks; ++k) {
+    const uint64_t lo = k * chunk, hi = std::min(n, lo + chunk), m = hi - lo;
+    const int s = (int)(k & 1);
+    if (k + 1 < nchunks && (rc = send(k + 1))) return leave(rc);
+    // decode: the wide columns of rows [lo, hi)
+    void* dcol[9] = {};
+    for (int c = 0; c < 9; ++c)
+      if (((present >> c) & 1) && (rc = hw(e, kHwCol + c, kPkEsz[c] * m, &dcol[c]))) return leave(rc);
+    void *d_status, *d_value;
+    if ((rc = hw(e, kHwStatus, m, &d_status)) || (rc = hw(e, kHwValue, 8 * m, &d_value))) return leave(rc);
+    hipError_t x = hipStreamWaitEvent(st, e->pk_landed[s], 0);
+    if (x == hipSuccess) x = stamp(k, 2, st);
+    if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: wait for the piece", x));
+    if (launch_unpack(unpack_args(piece[s], (const uint8_t*)piece[s] + piece_dir[s], piece_base[s], dcol, present),
+                      (uint32_t)((m + kB - 1) / kB), st))
+      return leave(set_err(CC_ERR_HIP, "unpack launch", hipGetLastError()));
+    x = stamp(k, 3, st);
+    // the wide rows stay in HBM (sentinels as in apply_host); chunk k - 1's encode has read them on this stream
+    if (x == hipSuccess) x = hipMemsetAsync(d_status, 0xFF, m, st);
+    if (x == hipSuccess) x = hipMemsetAsync(d_value, 0xA5, 8 * m, st);
+    // the chunk's events are appended to the device columns from the events so far on
+    const uint64_t used = std::min(ev_n, ev_capacity);
+    cc_events dev = acc;
+    dev.pos += used, dev.target += used, dev.code += used, dev.src += used, dev.tag += used, dev.payload += used;
+    dev.capacity -= used;
+    if (x == hipSuccess) x = hipMemsetAsync(dev.count, 0, sizeof(uint64_t), st);
+    if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: result prefill", x));
+    if ((rc = ckpt_save(e))) return leave(rc);
+    const cc_batch d{(const uint64_t*)dcol[0], (const uint64_t*)dcol[1], (const uint32_t*)dcol[2],
+                     (const uint8_t*)dcol[3],  (const uint8_t*)dcol[4],  (const uint64_t*)dcol[5],
+                     (const uint64_t*)dcol[6], (const uint64_t*)dcol[7], (const uint64_t*)dcol[8]};
+    const cc_results r{(uint8_t*)d_status, (uint64_t*)d_value};
+    (void)stamp(k, 4, st);
+    e->last_err_bits = 0;
+    rc = cc_apply_batch(e, &d, m, &r, &dev, st);
+    if (rc) {
+      (void)hipStreamSynchronize(st);
+      return leave(rc);
+    }
+    (void)stamp(k, 5, st);
+    // encode into staging s once its copy-out of chunk k - 2 is done; the total comes back with the chunk's checks
+    uint8_t* stage = nullptr;
+    if (k >= 2 && (x = hipStreamWaitEvent(st, e->pk_drained[s], 0)) != hipSuccess)
+      return leave(set_err(CC_ERR_HIP, "packed apply: wait for the result staging", x));
+    (void)stamp(k, 6, st);
+    if ((rc = rp_encode(e, kHwRes0 + s, d_status, d_value, m, res_data0 + res_data, st, &stage))) {
+      (void)hipStreamSynchronize(st);
+      return leave(rc);
+    }
+    (void)stamp(k, 7, st);
+    // the chunk's event count comes back with its checks too
+    if ((x = hipMemcpyAsync(e->ep_pin, dev.count, sizeof(uint64_t), hipMemcpyDeviceToHost, st)) != hipSuccess) {
+      (void)hipStreamSynchronize(st);
+      return leave(set_err(CC_ERR_HIP, "packed apply: event count read-back", x));
+    }
+    const int rs = cc_sync(e);  // device-side checks (capacity, unsupported ops, time order); the stream is drained
+    const uint64_t cnt = e->ep_pin[0];
+    int re = CC_OK;
+    if (cnt > dev.capacity) {
+      e->last_err_bits |= kErrEvents;  // (a full event stream, like a full max_events arena)
+      re = set_err(CC_ERR_CAPACITY, "more events than the host event stream holds");
+    }
+    ev_n += cnt;
+    rc = rs ? rs : re;
+    bool rolled_back = false;
+    if (rc == CC_ERR_CAPACITY) {  // a full event stream or map table region, and nothing else: not applied
+      const uint32_t bits = e->last_err_bits;
+      if (bits && !(bits & ~(kErrCapacity | kErrEvents))) {
+        const int rr = ckpt_restore(e);
+        if (rr) return leave(rr);
+        e->last_err_bits = bits;
+        rolled_back = true;
+      }
+    }
+    if (!rolled_back) {  // (a failing chunk that stays applied returns its rows, as cc_apply_batch_host does)
+      const uint64_t total = *e->rp_pin, db = rp_blocks(m) * sizeof(cc_respack_block);
+      if (total > 9 * m + 32)
+        return leave(set_err(CC_ERR_STATE, "internal check: the result blob encoder wrote past its bound"));
+      x = stamp(k, 8, e->pk_out);
+      if (x == hipSuccess)
+        x = hipMemcpyAsync(res + sizeof(cc_pack_header) + (lo / kB) * sizeof(cc_respack_block), stage + kRpHead, db,
+                           hipMemcpyDeviceToHost, e->pk_out);
+      if (x == hipSuccess && total)
+        x = hipMemcpyAsync(res + res_data0 + res_data, stage + kRpHead + db, total, hipMemcpyDeviceToHost, e->pk_out);
+      if (x == hipSuccess) x = stamp(k, 9, e->pk_out);
+      if (x == hipSuccess) x = hipEventRecord(e->pk_drained[s], e->pk_out);
+      if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: result blob copy-out", x));
+      res_rows = hi, res_data += total;
+    }
+    if (rc) return leave(rc);
+    // the chunk is applied: its events stay, their rows as batch positions
+    if (lo && cnt && launch_ev_shift(dev.pos, cnt, (uint32_t)lo, st))
+      return leave(set_err(CC_ERR_HIP, "event row shift launch", hipGetLastError()));
+    ev_kept = ev_n;
+    if (h_rows_done) *h_rows_done = hi;
+    e->ep_chunks = stamps ? k + 1 : 0;
+  }
+  return leave(CC_OK);
+}
+
+extern "C" int cc_packed_events_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms) {
+  if (!e || !chunks || (cap && !h_ms)) return set_err(CC_ERR_INVALID, "null argument");
+  HIPCHECK(hipSetDevice(e->device));
+  *chunks = e->ep_chunks;
+  float call_ms[2] = {0, 0};
+  if (e->ep_chunks)
+    for (int j = 0; j < 2; ++j)
+      HIPCHECK(hipEventElapsedTime(call_ms + j, e->ep_call_stamp[2 * j], e->ep_call_stamp[2 * j + 1]));
+  for (uint64_t k = 0; k < std::min(cap, e->ep_chunks); ++k) {
+    for (int j = 0; j < 5; ++j)
+      HIPCHECK(hipEventElapsedTime(h_ms + 7 * k + j, e->ep_stamp[10 * k + 2 * j], e->ep_stamp[10 * k + 2 * j + 1]));
+    h_ms[7 * k + 5] = call_ms[0], h_ms[7 * k + 6] = call_ms[1];
+  }
   return CC_OK;
 }
 

@@ -125,6 +125,13 @@ def lib():
             "cc_respack_from_device": (i32, [P, P, u64, P, u64, P, P]),
             "cc_apply_batch_host_packed_results": (i32, [P, P, u64, P, u64, P, P, P, P]),
             "cc_packed_results_timeline": (i32, [P, u64, P, P]),
+            "cc_evpack_bound": (i32, [u64, P]),
+            "cc_evpack_pack": (i32, [P, u64, P, u64, u32, P]),
+            "cc_evpack_check": (i32, [P, u64, P]),
+            "cc_evpack_unpack": (i32, [P, u64, P, u32]),
+            "cc_evpack_from_device": (i32, [P, P, P, u64, P, P, P]),
+            "cc_apply_batch_host_packed_events": (i32, [P, P, u64, P, u64, P, P, u64, u64, P, P, P, P]),
+            "cc_packed_events_timeline": (i32, [P, u64, P, P]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -492,6 +499,58 @@ class Engine:
         _check(self.L.cc_packed_results_timeline(self.h, 0, C.byref(n), None))
         ms = np.zeros((max(n.value, 1), 5), np.float32)
         _check(self.L.cc_packed_results_timeline(self.h, n.value, C.byref(n), _np(ms)))
+        return ms[:n.value]
+
+    def events_to_host_packed(self, events, stream=None, out=None):
+        """cc_evpack_from_device: a device event stream (DeviceEvents) -> (event_blob, count): a packed event blob in
+        host memory (batch.unpack_events decodes it), byte for byte batch.pack_events of the first min(count, capacity)
+        events, and the device count.  Synchronous.  count > capacity raises EngineError (CC_ERR_CAPACITY) carrying the
+        blob of the first `capacity` events as .blob and the count as .count.  `out`: a 16-byte-aligned uint8 buffer of
+        at least batch.events_bound(events.capacity) bytes."""
+        from .batch import _aligned_bytes, events_bound
+
+        blob = out if out is not None else _aligned_bytes(events_bound(events.capacity))
+        s = events.struct()
+        size, count = C.c_uint64(), C.c_uint64()
+        rc = self.L.cc_evpack_from_device(self.h, C.byref(s), blob.ctypes.data, blob.nbytes, C.byref(size), C.byref(count),
+                                          _stream_ptr(stream))
+        if rc == abi.CC_ERR_CAPACITY and size.value <= blob.nbytes and count.value > events.capacity:
+            err = EngineError(rc, lib().cc_last_error().decode(errors="replace"))
+            err.blob, err.count = blob[:size.value], count.value
+            raise err
+        _check(rc)
+        return blob[:size.value], count.value
+
+    def apply_host_packed_events(self, blob, n, capacity=None, chunk_rows=0, out=None, ev_out=None, timeline=False):
+        """cc_apply_batch_host_packed_events: apply_host_packed_results with the events as a packed event blob of at most
+        `capacity` events.  Returns (result_blob, event_blob, ev_count, rows_done): batch.unpack_events(event_blob) gives
+        the events of the chunks fully applied (pos = batch rows); ev_count is what the wide call leaves in its event
+        count.  `out` / `ev_out`: 16-byte-aligned uint8 buffers of at least batch.results_bound(n) /
+        batch.events_bound(capacity) bytes (e.g. page-locked with host_register)."""
+        from .batch import _aligned_bytes, events_bound, results_bound
+
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        cap = capacity if capacity is not None else max(4 * n, 1024)
+        res = out if out is not None else _aligned_bytes(results_bound(n))
+        evb = ev_out if ev_out is not None else _aligned_bytes(events_bound(cap))
+        opts = abi.cc_packed_opts(chunk_rows=chunk_rows, flags=abi.CC_PACKED_TIMELINE if timeline else 0)
+        done, size, ev_size, ev_count = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = self.L.cc_apply_batch_host_packed_events(self.h, blob.ctypes.data, blob.nbytes, res.ctypes.data, res.nbytes,
+                                                      C.byref(size), evb.ctypes.data, cap, evb.nbytes, C.byref(ev_size),
+                                                      C.byref(ev_count), C.byref(opts), C.byref(done))
+        if rc != abi.CC_OK and not (rc == abi.CC_ERR_CAPACITY and done.value < n and size.value <= res.nbytes
+                                    and ev_size.value <= evb.nbytes):
+            _check(rc)
+        return res[:size.value], evb[:ev_size.value], ev_count.value, done.value
+
+    def packed_events_timeline(self):
+        """Per chunk of the last apply_host_packed_events(timeline=True): (H2D, decode, apply, result encode, result D2H,
+        event encode, event D2H) milliseconds; the event blob is encoded and sent once per call, so the last two figures
+        are the call's in every row."""
+        n = C.c_uint64()
+        _check(self.L.cc_packed_events_timeline(self.h, 0, C.byref(n), None))
+        ms = np.zeros((max(n.value, 1), 7), np.float32)
+        _check(self.L.cc_packed_events_timeline(self.h, n.value, C.byref(n), _np(ms)))
         return ms[:n.value]
 
     def unpack_to_device(self, blob, cols, stream=None):

@@ -790,6 +790,96 @@ int  cc_apply_batch_host_packed_results(cc_engine* e, const void* h_blob, uint64
  * chunks that completed; h_ms (5 floats per chunk, room for cap chunks) = H2D, decode, apply, encode, D2H ms. */
 int  cc_packed_results_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms);
 
+/* ---- packed event blobs (copycat_amd/csrc/evpack.cpp, evpack.hip, host_path.hip) -------------------------------------
+ * The event-blob calls exist from this commit on, under the unchanged CC_ABI_VERSION 6 (symbols are only added).
+ * A cc_events row is 19 B wide (pos, target u32; code, src, tag u8; payload u64), and a fan-out (a topic publish, a
+ * group join or leave) writes one row per listener: the event stream is the widest of a host's three streams.  Inside
+ * a block of consecutive events pos is non-decreasing and spans few rows, code / src / tag are one value or a few,
+ * target spans the instance slots of a few resources, and a fan-out's payload is one value per publishing row.  A
+ * gfx950 encoder (evpack.hip) writes the blob in HBM and only the narrow bytes travel D2H.
+ *
+ * One contiguous, 16-byte-aligned blob:  header | directory | data
+ *   header     cc_pack_header (64 B): magic CC_EVPACK_MAGIC, version CC_EVPACK_VERSION, n = events, present = 0x3F,
+ *              block_rows = CC_PACK_BLOCK_ROWS
+ *   directory  cc_evpack_block[blocks] (112 B each), block k = events [4096 k, min(n, 4096 (k + 1)))
+ *   data       per block one data area; the six columns lie in it in cc_events order (pos, target, code, src, tag,
+ *              payload), each rows * width bytes (or its table, below) rounded up to 16, the padding zero
+ * Every offset is a multiple of 16; block areas lie back to back from the directory's end, in block order.
+ *   CC_PK_FOR     value = base + zero_extend(offset), modulo the column's native width
+ *                   pos, target     widths 0, 1, 2, 4; 4 is the raw column with base 0; base = the unsigned minimum
+ *                   code, src, tag  widths 0, 1; 1 is the raw column with base 0
+ *                   payload         widths 0, 1, 2, 4, 8; 8 is the raw column with base 0; the narrowest of base = the
+ *                                   unsigned minimum and base = the signed minimum, a tie to the unsigned base (the
+ *                                   result blob's value rule)
+ *   CC_PK_BY_POS  payload only: the column is a table indexed by the row's pos offset,
+ *                   payload[row] = base + zero_extend(table[pos[row] - pos.base])
+ *                 cc_pack_col.reserved16 = the table's entries E, the stored bytes are r16(E * width), an entry no row
+ *                 refers to is 0.  Legal only when the block's pos column has width 0, 1 or 2.  The encoder may use it
+ *                 when for every row i >= 1 of the block pos[i] >= pos[i-1], and pos[i] == pos[i-1] implies
+ *                 payload[i] == payload[i-1]; then E = pos_max - pos_min + 1, base and width are the FOR rule's, and
+ *                 it is chosen iff width > 0 and r16(E * width) < r16(rows * width) (a tie goes to FOR).
+ * A row is decodable on its own: one directory entry, one pos read and (BY_POS) one table read.  Decoding reproduces
+ * the six columns byte for byte for every input; there is no escape path.  The blob of a full encode is a function of
+ * the event columns alone: the host encoder at any thread count, the kernels and the pipelined call at any chunking
+ * write the same bytes. */
+#define CC_EVPACK_MAGIC    1162888003  /* "CCPE" little-endian */
+#define CC_EVPACK_VERSION  1
+#define CC_EVPACK_COLUMNS  6
+#define CC_PK_BY_POS       2
+
+typedef struct cc_evpack_block {
+  uint32_t rows;        /* CC_PACK_BLOCK_ROWS, or the tail's */
+  uint32_t bytes;       /* length of the block's data area */
+  uint64_t offset;      /* of the block's data area from the blob start */
+  cc_pack_col col[6];   /* pos, target, code, src, tag, payload */
+} cc_evpack_block;
+
+/* Host side, no GPU involved.  cc_evpack_bound: the worst-case blob size of n events.  cc_evpack_pack: the reference
+ * encoder; it takes h_events' column pointers only (capacity and count are ignored), n events -> h_blob (16-byte
+ * aligned, cap bytes); *bytes = the blob's size; a cap too small returns CC_ERR_CAPACITY with *bytes = the size needed
+ * and writes nothing.  cc_evpack_check: the single validator (every check cc_respack_check makes, and for BY_POS:
+ * payload column only, pos width <= 2, 1 <= E <= 4096, table bytes = r16(E * width), every pos offset of the block
+ * < E); any violation is CC_ERR_INVALID with a message that names the "event blob"; *n optional.  A blob that passes
+ * decodes with no read outside `bytes` and no write outside n rows.  cc_evpack_unpack: the host decoder (validator
+ * first; h_out->capacity >= n or CC_ERR_CAPACITY; *h_out->count = n when count is non-NULL). */
+int  cc_evpack_bound(uint64_t n, uint64_t* bytes);
+int  cc_evpack_pack(const cc_events* h_events, uint64_t n, void* h_blob, uint64_t cap, uint32_t threads, uint64_t* bytes);
+int  cc_evpack_check(const void* h_blob, uint64_t bytes, uint64_t* n);
+int  cc_evpack_unpack(const void* h_blob, uint64_t bytes, const cc_events* h_out, uint32_t threads);
+
+/* Encode a device event stream (d_events: device columns, pos / target / payload 16-byte aligned, and its device count
+ * word) into an event blob in the caller's host memory, for hosts that keep columns resident (after cc_apply_batch,
+ * cc_apply_batch_prefix, cc_sessions_close / cc_sessions_expire, cc_advance_time_events) but take events over PCIe.
+ * The call drains `stream`, reads *d_events->count, encodes min(count, capacity) events in engine-owned staging and
+ * copies only header + directory + used data bytes.  Synchronous; the blob is byte for byte cc_evpack_pack's.  *count
+ * (optional) = the device count; when it exceeds capacity the call returns CC_ERR_CAPACITY after writing the first
+ * `capacity` events' blob, as the wide host forms do.  cap_bytes < cc_evpack_bound(capacity): CC_ERR_CAPACITY with
+ * *bytes = the bound, before any launch.  Zero events: a header-only blob. */
+int  cc_evpack_from_device(cc_engine* e, const cc_events* d_events, void* h_blob, uint64_t cap_bytes, uint64_t* bytes,
+                           uint64_t* count, void* stream);
+
+/* cc_apply_batch_host_packed_results with the host event stream replaced by an event blob of at most ev_capacity
+ * events.  State, result blob, applied index, *h_rows_done and the return code are exactly those of that call made with
+ * a wide host event stream of capacity = ev_capacity; *ev_count is what it leaves in *h_events->count.  Every chunk's
+ * events are appended to engine-owned device columns after those of the chunks before, pos is shifted to batch rows on
+ * the device, and no wide event byte crosses PCIe.  On every return after argument validation h_ev_blob is a valid
+ * event blob (*ev_bytes its size) of the events of rows [0, *h_rows_done), the chunks fully applied; a failing or
+ * rolled-back chunk's events are not in it.  Decoded, it equals the first header.n rows of the wide call's event
+ * columns byte for byte, and its bytes do not depend on the chunking.  The blob is encoded once, after the last chunk,
+ * and leaves in one D2H: the directory's length, and with it every data offset, is known only with the last chunk's
+ * count.  h_ev_blob NULL or not 16-byte aligned, ev_bytes or ev_count NULL: CC_ERR_INVALID; ev_cap_bytes <
+ * cc_evpack_bound(ev_capacity): CC_ERR_CAPACITY with *ev_bytes = the bound, before anything is copied or launched. */
+int  cc_apply_batch_host_packed_events(cc_engine* e, const void* h_blob, uint64_t bytes, void* h_res_blob,
+                                       uint64_t res_cap, uint64_t* res_bytes, void* h_ev_blob, uint64_t ev_capacity,
+                                       uint64_t ev_cap_bytes, uint64_t* ev_bytes, uint64_t* ev_count,
+                                       const cc_packed_opts* opts, uint64_t* h_rows_done);
+
+/* The stage times of the last cc_apply_batch_host_packed_events call made with CC_PACKED_TIMELINE: *chunks = the
+ * chunks that completed; h_ms (7 floats per chunk, room for cap chunks) = H2D, decode, apply, result encode, result
+ * D2H, event encode, event D2H milliseconds.  The event blob is encoded and sent once per call: the last two figures
+ * are the call's, repeated in every chunk's row. */
+int  cc_packed_events_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms);
+
 #ifdef __cplusplus
 }
 #endif
