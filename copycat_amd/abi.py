@@ -26,6 +26,7 @@ CC_RES_SET = 6
 CC_RES_QUEUE = 7
 CC_RES_MULTIMAP = 8
 CC_RES_TOPIC = 9
+CC_RES_BUS = 10
 CC_QUEUE_CAP = 64
 
 CC_OP_DELETE = 1
@@ -86,6 +87,11 @@ CC_OP_GROUP_EXECUTE = 123
 CC_OP_TOPIC_LISTEN = 125
 CC_OP_TOPIC_UNLISTEN = 126
 CC_OP_TOPIC_PUBLISH = 127
+CC_OP_BUS_JOIN = 85
+CC_OP_BUS_LEAVE = 86
+CC_OP_BUS_REGISTER = 87
+CC_OP_BUS_UNREGISTER = 88
+CC_BUS_HANDLE_BITS = 32
 
 CC_TAG_NULL = 0
 CC_TAG_LONG = 1
@@ -94,6 +100,7 @@ CC_TAG_BOOL = 3
 CC_TAG_HANDLE = 4
 CC_TAG_SET = 5
 CC_TAG_LIST = 6
+CC_TAG_MAP = 7
 
 CC_ST_OK = 0
 CC_ST_UNKNOWN_SESSION = 1
@@ -113,6 +120,11 @@ CC_EV_LEAVE = 5
 CC_EV_EXECUTE = 6
 CC_EV_MEMBER = 7
 CC_EV_MESSAGE = 8
+CC_EV_BUS_LEAVE = 9
+CC_EV_BUS_REGISTER = 10
+CC_EV_BUS_UNREGISTER = 11
+CC_EV_BUS_TOPIC = 12
+CC_EV_BUS_ADDRESS = 13
 
 CC_EVSRC_COMMIT = 0
 CC_EVSRC_TIMER = 1
@@ -127,6 +139,7 @@ CC_ELECTION_LISTENERS = 64
 CC_GROUP_MEMBERS = 64
 CC_VALUE_LISTENERS = 64
 CC_TOPIC_LISTENERS = 64
+CC_BUS_ENTRIES = 64
 
 # ops each resource type registers (ResourceStateMachine.init + Copycat reflection `configure`)
 TYPE_OPS = {
@@ -141,6 +154,8 @@ TYPE_OPS = {
 }
 # TopicState's ops (TopicCommands.java:53,64,80); kept beside TYPE_OPS, whose ops the wire fixture must all contain
 TOPIC_OPS = {CC_OP_DELETE, 125, 126, 127}
+# MessageBusState's ops (MessageBusCommands.java; 89 is ConsumerInfo, not an op)
+BUS_OPS = {CC_OP_DELETE, 85, 86, 87, 88}
 # key tags of the flags column (keys are never null)
 KTAG_OF_TAG = {CC_TAG_LONG: 0, CC_TAG_INT: 1, CC_TAG_BOOL: 2, CC_TAG_HANDLE: 3}
 TAG_OF_KTAG = {v: k for k, v in KTAG_OF_TAG.items()}

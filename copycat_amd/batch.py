@@ -348,6 +348,8 @@ def untagged(tag, payload):
         return Handle(payload)
     if tag == abi.CC_TAG_SET:
         return ("set", payload)
+    if tag == abi.CC_TAG_MAP:  # MessageBusState.join: the topic count; the rows are in the event stream
+        return ("map", payload)
     raise ValueError(f"unknown tag {tag}")
 
 

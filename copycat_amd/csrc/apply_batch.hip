@@ -497,13 +497,16 @@ int Batch::list_rows(uint32_t& nb) {
   }
   nb = l.nb;
   // The leak log (commits dropped without clean()) is drained before every batch of an engine that can add to it:
-  // every multimap put, and with value events every re-listen (AtomicValueState.listen :41-49) may land there, at
-  // most one entry per row, so the drained log gets room for n more; a coordination engine without value events
+  // every multimap put, every bus unregister, and with value events every re-listen (AtomicValueState.listen :41-49) may land
+  // there, at most one entry per row, so the drained log gets room for n more; a coordination engine without value events
   // adds entries only in the close fan-out (cc_sessions_close sizes the log for that itself) but is drained here
   // too, so nothing accumulates across batches toward the log's end.
   if (e->has_mmaps || e->coord_on) {
     TRY(drain_leaks(e));
-    if (e->has_mmaps || (e->cfg.flags & CC_CFG_VALUE_EVENTS)) TRY(ensure_leak(e, n));
+    // (a bus row drops at most its own or the commit it replaces, and a leave the leaver's registrations besides:
+    // entries the buses held before the batch, or rows of the batch that dropped nothing of their own)
+    const uint64_t held = std::min<uint64_t>(n, e->bus_slots) * e->coord_cap;
+    if (e->has_mmaps || e->bus_slots || (e->cfg.flags & CC_CFG_VALUE_EVENTS)) TRY(ensure_leak(e, n + held));
   }
   return CC_OK;
 }
@@ -1107,8 +1110,10 @@ int Batch::sub_coord(Sub& s) {
   ca.leak_n = e->d_leak_n;
   ca.leak_cap = e->leak_cap;
   ca.fx = e->d_fan;
+  ca.bus = e->bus_slots != 0;
   if (!e->has_topics) return launched(launch_apply_coord(ca, st), "coordination apply launch", st);
-  // TopicState.publish: the walk leaves one fan record per publish, k_topic_fanout expands them into the arena
+  // TopicState.publish, MessageBusState register / unregister / leave: the walk leaves fan records, k_topic_fanout
+  // expands them into the arena
   HIPCHECK(hipMemsetAsync(e->d_fan, 0, offsetof(FanCtx, cap), st));
   TRY(launched(launch_apply_coord(ca, st), "coordination apply launch", st));
   FanoutArgs fa{};

@@ -1,5 +1,5 @@
 // apply_coord.hip — coordination state machines (LockState, LeaderElectionState, MembershipGroupState, QueueState,
-// TopicState) and AtomicValue with listeners, with their published events.
+// TopicState, MessageBusState) and AtomicValue with listeners, with their published events.
 //
 // Like apply_value.hip, one thread owns one resource slot and applies that slot's commits in log order; here a
 // workgroup owns a quarter super-bucket (64 slots, see k_apply_coord).  The super-buckets handled here are those holding a
@@ -22,7 +22,9 @@
 //   AtomicValueState.listen :41-49, unlisten :54-63, change :68-72, get/set/compareAndSet/getAndSet :77-144;
 //   TopicState.listen :42-48 (a second listen of an instance is clean()ed, the first stays), unlisten :53-62,
 //   publish :67-82 (one "message" per listener: not emitted here but left as one fan record for k_topic_fanout,
-//   topic_fanout.hip), delete :85-88, close :35-37 (close.hip).
+//   topic_fanout.hip), delete :85-88, close :35-37 (close.hip);
+//   MessageBusState.join :45-65 (Map<String, Set<Address>> result rows), leave :70-97, registerConsumer :102-119,
+//   unregisterConsumer :124-144 (their ConsumerInfo fan-outs: fan records too), delete :147-151, close :35-40 (close.hip).
 // Lock timeouts: a waiter whose deadline (clock at lock + timeout) is <= the clock at which due timers fire
 // before a commit (the previous commit's clock in manager mode, this commit's in module mode, A8) is gone
 // before that commit is applied; they publish nothing, so applying them lazily per lock is exact.
@@ -212,7 +214,7 @@ struct Rec {
 
 // T != 0: the resource type is known at compile time (a wave whose slots all hold one type walks a specialised
 // copy with no code for the other types); T == 0: the runtime `type`.
-template <uint32_t T>
+template <uint32_t T, bool kBus>
 __device__ inline uint32_t coord_apply(uint32_t type_rt, uint32_t slot, const Rec& r, CoordHdr& h, const Ents& E,
                                        uint32_t& vmeta_s, uint64_t& vval, uint64_t& rv, uint32_t& nev, const Emitter& em,
                                        uint32_t& lane_n, uint32_t& err) {
@@ -291,7 +293,7 @@ __device__ inline uint32_t coord_apply(uint32_t type_rt, uint32_t slot, const Re
       return CC_STATUS(CC_ST_OK, CC_TAG_BOOL);
     }
   }
-  if (!op_registered(type, r.op)) return CC_STATUS(CC_ST_UNKNOWN_OP, CC_TAG_NULL);
+  if (!op_registered<kBus>(type, r.op)) return CC_STATUS(CC_ST_UNKNOWN_OP, CC_TAG_NULL);
   switch (type) {
     case CC_RES_LOCK: {
       const uint64_t fire = r.a, clk = r.key;
@@ -652,7 +654,7 @@ __device__ inline uint32_t coord_apply(uint32_t type_rt, uint32_t slot, const Re
           const unsigned long long q = atomicAdd(&fx->rec_n, 1ull);  // one atomic per record
           if ((h.flags & kCoSnap) && q < fx->cap) {  // (else more events than the arena holds: k_topic_fanout fails the call)
             const uint32_t tg = CC_FLAG_TAG_A(r.flags);
-            fx->rec[q] = FanRec{r.g, n, tg == CC_TAG_NULL ? 0 : r.a, h.who, tg};
+            fx->rec[q] = FanRec{r.g, n, tg == CC_TAG_NULL ? 0 : r.a, h.who, fan_tag(tg, CC_EV_MESSAGE, 0)};
           }
         }
         nev = n;
@@ -682,6 +684,181 @@ __device__ inline uint32_t coord_apply(uint32_t type_rt, uint32_t slot, const Re
       }
       return CC_STATUS(CC_ST_OK, CC_TAG_NULL);
     }
+    case CC_RES_BUS: if constexpr (T == CC_RES_BUS) {  // MessageBusState.java:30-153 (its own walk only: k_apply_coord)
+      // Two collections in one block (layout: common.h, kBusCleaned): `members` keyed by commit.session().id() (the
+      // instance id, as for a topic) from the front, `topics` -> registrations from the back.  register / unregister /
+      // leave publish a ConsumerInfo(topic, address) to every member: like a topic's publish they leave FanRecs against
+      // a snapshot of the members' instance slots, retaken only after the member list changed (a new member's join, a
+      // leave; delete() and a re-join keep the list), and k_topic_fanout writes the events in ascending member id.
+      // A bus's entries are read and written straight in the global block (k_apply_coord keeps none of them in the
+      // lane's register / LDS entries, see its E.store): both ends of the block are in use, and one plain access per
+      // site keeps the walk's code and registers where the other types left them.
+      GlbEnt* const G = E.glb;
+      const uint32_t top = E.cap - 1;  // registration j sits in G[top - j]
+      auto cp = [&](uint32_t d, uint32_t s) {
+        G[d].x = G[s].x;
+        G[d].idx = G[s].idx;
+        G[d].inst = G[s].inst;
+        G[d].pad = G[s].pad;
+      };
+      auto set = [&](uint32_t d, uint64_t x, uint64_t idx, uint32_t inst, uint32_t pad) {
+        G[d].x = x;
+        G[d].idx = idx;
+        G[d].inst = inst;
+        G[d].pad = pad;
+      };
+      auto member_at = [&](uint64_t id, uint32_t& pos) -> bool {  // members sorted by instance id
+        uint32_t lo = 0, hi = h.n;
+        while (lo < hi) {
+          const uint32_t m = (lo + hi) >> 1;
+          if (G[m].x < id) lo = m + 1; else hi = m;
+        }
+        pos = lo;
+        return lo < h.n && G[lo].x == id;
+      };
+      auto fan = [&](uint32_t code, uint64_t payload, uint32_t first) {  // one fan-out to the h.n > 0 members
+        FanCtx* fx = em.fx;
+        const uint32_t n = h.n;
+        if (!(h.flags & kCoSnap)) {  // one atomic per snapshot
+          const unsigned long long o = atomicAdd(&fx->log_n, (unsigned long long)n);
+          if (o + n <= fx->cap) {
+            uint32_t* lg = fx->log + o;
+            for (uint32_t i = 0; i < n; ++i) lg[i] = G[i].inst;
+            h.who = (uint32_t)o;
+            h.flags |= kCoSnap;
+          }
+        }
+        const unsigned long long q = atomicAdd(&fx->rec_n, 1ull);  // one atomic per record
+        if ((h.flags & kCoSnap) && q < fx->cap)  // (else more events than the arena holds: k_topic_fanout fails the call)
+          fx->rec[q] = FanRec{r.g, n, payload, h.who, fan_tag(CC_TAG_HANDLE, code, first)};
+      };
+      if (r.op == CC_OP_DELETE) {  // delete :147-151: every Join and Register clean()ed, topics cleared, members kept
+        for (uint32_t i = 0; i < h.n; ++i) G[i].idx |= kBusCleaned;
+        h.head = 0;
+        return CC_STATUS(CC_ST_OK, CC_TAG_NULL);
+      }
+      // the operand (Join: the address, Register / Unregister: the topic) is a handle below 2^32: a ConsumerInfo is
+      // one 64-bit payload, and the handle sits in CoordEnt.pad
+      if (r.op != CC_OP_BUS_LEAVE && (CC_FLAG_TAG_A(r.flags) != CC_TAG_HANDLE || (r.a >> CC_BUS_HANDLE_BITS))) {
+        err |= kErrUnsupported;
+        return CC_STATUS(CC_ST_OK, CC_TAG_NULL);
+      }
+      uint32_t mp = 0;
+      const bool member = member_at(r.iid, mp);
+      if (r.op == CC_OP_BUS_JOIN) {  // join :45-65
+        if (member) {  // members.put over an entry: the old Join is not clean()ed (leaked unless delete() cleaned it)
+          const uint64_t old = G[mp].idx;
+          if (!(old & kBusCleaned)) em.leaked(slot, old, err);
+        } else {
+          // (at coord_cap 65,536 a bus holds 65,535 members: a close's "leave" fan-out is counted in 16 bits too)
+          if (h.n + h.head > top || h.n >= kBusEvMax || !bus_product_ok(h.n + 1, h.head)) {
+            err |= kErrCoordFull;
+            return CC_STATUS(CC_ST_OK, CC_TAG_NULL);
+          }
+          for (uint32_t i = h.n; i > mp; --i) cp(i, i - 1);
+          ++h.n;
+          h.flags &= ~kCoSnap;
+        }
+        set(mp, r.iid, r.idx, r.inst, (uint32_t)r.a);
+        // the returned Map<String, Set<Address>> :49-60 as result rows: every topic (one with no member among its
+        // registrants, or with an empty registration map, maps to an empty set), ascending; under each the distinct
+        // addresses of its registrants that are members now, ascending (one selection pass per distinct address)
+        uint32_t j = 0;
+        while (j < h.head) {
+          const uint32_t topic = G[top - j].pad;
+          em.emit(lane_n, r.g, nev++, r.inst, CC_EV_BUS_TOPIC, CC_EVSRC_RESULT, CC_TAG_HANDLE, topic);
+          ++rv;
+          uint64_t above = 0;  // addresses below this one are out (address + 1, so 0 = none yet)
+          uint32_t j1;
+          for (;;) {
+            uint64_t best = ~0ull;
+            for (j1 = j; j1 < h.head && G[top - j1].pad == topic; ++j1) {
+              const uint64_t id = G[top - j1].x;
+              uint32_t p = 0;
+              if (!id || !member_at(id, p)) continue;  // an empty-topic marker / a registrant whose session closed
+              const uint64_t a = G[p].pad;
+              if (a >= above && a < best) best = a;
+            }
+            if (best == ~0ull) break;
+            em.emit(lane_n, r.g, nev++, r.inst, CC_EV_BUS_ADDRESS, CC_EVSRC_RESULT, CC_TAG_HANDLE, best);
+            above = best + 1;
+          }
+          j = j1;
+        }
+        return CC_STATUS(CC_ST_OK, CC_TAG_MAP);
+      }
+      if (r.op == CC_OP_BUS_LEAVE) {  // leave :70-97 (the Leave commit is always clean()ed)
+        if (!member) return CC_STATUS(CC_ST_OK, CC_TAG_NULL);
+        const uint64_t addr = G[mp].pad;  // previous.operation().member(); previous.clean()
+        for (uint32_t i = mp + 1; i < h.n; ++i) cp(i - 1, i);
+        --h.n;
+        h.flags &= ~kCoSnap;
+        // every topic the leaver is registered on, in ascending topic handle (engine-defined): the registration is
+        // removed without clean() (leaked), "unregister" goes to every remaining member, and a topic left with no
+        // registration is dropped (a topic that was empty before stays: its marker is kept)
+        uint32_t kept = 0;
+        for (uint32_t j = 0; j < h.head; ++j) {
+          if (G[top - j].x == r.iid) {
+            em.leaked(slot, G[top - j].idx, err);
+            if (h.n) {
+              fan(CC_EV_BUS_UNREGISTER, ((uint64_t)G[top - j].pad << 32) | addr, nev);
+              nev += h.n;
+            }
+            continue;
+          }
+          if (kept != j) cp(top - kept, top - j);
+          ++kept;
+        }
+        h.head = kept;
+        return CC_STATUS(CC_ST_OK, CC_TAG_NULL);
+      }
+      // registerConsumer :102-119 / unregisterConsumer :124-144: the session's registration on the topic
+      const uint32_t topic = (uint32_t)r.a;
+      const bool add = r.op == CC_OP_BUS_REGISTER;
+      if (add && !member) return CC_STATUS(CC_ST_ILLEGAL_STATE, CC_TAG_NULL);  // "unknown session", the commit clean()ed
+      // the Unregister commit is clean()ed only on the exception path: the log retains every one of them
+      if (!add) em.leaked(slot, r.idx, err);
+      uint32_t rp = 0, hi = h.head;  // registrations sorted by (topic, instance id)
+      while (rp < hi) {
+        const uint32_t m = (rp + hi) >> 1;
+        const uint32_t tp = G[top - m].pad;
+        if (tp < topic || (tp == topic && G[top - m].x < r.iid)) rp = m + 1; else hi = m;
+      }
+      const bool hit = rp < h.head && G[top - rp].pad == topic && G[top - rp].x == r.iid;
+      bool publish = add;
+      if (add) {
+        // the marker of an empty topic is the topic's only entry, so it sorts right before (topic, id)
+        const bool marker = !hit && rp > 0 && G[top - rp + 1].pad == topic && G[top - rp + 1].x == 0;
+        if (hit) {  // registrations.put over an entry: the old Register is not clean()ed
+          em.leaked(slot, G[top - rp].idx, err);
+        } else if (marker) {
+          --rp;
+        } else {
+          if (h.n + h.head > top || !bus_product_ok(h.n, h.head + 1)) {
+            err |= kErrCoordFull;
+            return CC_STATUS(CC_ST_OK, CC_TAG_NULL);
+          }
+          for (uint32_t q = h.head; q > rp; --q) cp(top - q, top - q + 1);
+          ++h.head;
+        }
+        set(top - rp, r.iid, r.idx, r.inst, topic);
+      } else if (hit) {  // registrations.remove + registration.clean(); the topic stays even when it is empty now
+        const bool only = (rp == 0 || G[top - rp + 1].pad != topic) && (rp + 1 >= h.head || G[top - rp - 1].pad != topic);
+        if (only) {
+          set(top - rp, 0, 0, 0, topic);
+        } else {
+          for (uint32_t q = rp + 1; q < h.head; ++q) cp(top - q + 1, top - q);
+          --h.head;
+        }
+        publish = member;  // parent != null :133
+      }
+      if (publish) {  // "register" / "unregister"(ConsumerInfo) to every member, the committing one included
+        fan(add ? CC_EV_BUS_REGISTER : CC_EV_BUS_UNREGISTER, ((uint64_t)topic << 32) | G[mp].pad, 0);
+        nev = h.n;
+      }
+      return CC_STATUS(CC_ST_OK, CC_TAG_NULL);
+    }
+    break;
   }
   return CC_STATUS(CC_ST_UNKNOWN_OP, CC_TAG_NULL);
 }
@@ -714,6 +891,13 @@ constexpr int kCCh2 = kCT2 * kCPer2;       // 512 commits of the super-bucket pe
 // overflowed every chunk)
 constexpr int kEvLane = 11;  // (LDS 52,800 B: three workgroups per CU need <= 53,248 at the 2 KiB allocation granularity)
 
+// kBus: the instantiation launched on an engine that holds a MessageBusState (CoordArgs.bus).  The walk's registers
+// are the kernel's budget (165 of the 168 that three workgroups per CU leave), and one more specialised
+// walk did not fit beside the others: adding the bus walk alone cost 2 spilled VGPRs (12 B of scratch), the bus case in
+// the generic walk too 28.  So the bus has its specialised walk only, run after the other lanes' walk (lanes are
+// independent slots, so the order between lanes is free), and in this instantiation value slots walk the generic copy
+// instead of their own, which is what made room.  Engines without a bus run the kBus = false code, which has none of it.
+template <bool kBus>
 __global__ __launch_bounds__(kCT2, 3) void k_apply_coord(const XRec* __restrict__ xr, const uint16_t* __restrict__ ttab,
                                                      uint32_t tiles, uint32_t sb, uint32_t sbq_base,
                                                      const uint8_t* __restrict__ sb_kind,
@@ -949,6 +1133,12 @@ __global__ __launch_bounds__(kCT2, 3) void k_apply_coord(const XRec* __restrict_
       const uint32_t b = sstart[l], e = sstart[l + 1];
       auto walk = [&](auto tc) {
       for (uint32_t p = b; p < e; ++p) {
+        if constexpr (kBus && decltype(tc)::value == 0) {  // (a bus lane walks in the bus walk below)
+          if (type == CC_RES_BUS) break;
+        }
+        if constexpr (decltype(tc)::value == CC_RES_BUS) {
+          if (type != CC_RES_BUS) break;
+        }
         const uint32_t mmr = rmeta[p];
         Rec r;
         r.op = smeta_op(mmr);
@@ -962,7 +1152,7 @@ __global__ __launch_bounds__(kCT2, 3) void k_apply_coord(const XRec* __restrict_
         r.iid = riid[p];
         uint64_t rv;
         uint32_t nev = 0;
-        const uint32_t st = coord_apply<decltype(tc)::value>(type, res, r, h, E, vm, vv, rv, nev, em, lane_n, err);
+        const uint32_t st = coord_apply<decltype(tc)::value, kBus>(type, res, r, h, E, vm, vv, rv, nev, em, lane_n, err);
         rab[p] = u64x2{rv, (uint64_t)(st & 0xFFu) | ((uint64_t)(nev & 0xFFFFu) << 8)};  // the result over the record
       }
       };
@@ -981,9 +1171,12 @@ __global__ __launch_bounds__(kCT2, 3) void k_apply_coord(const XRec* __restrict_
       else if (wt == CC_RES_LOCK) walk(TypeC<CC_RES_LOCK>{});
       else if (wt == CC_RES_ELECTION) walk(TypeC<CC_RES_ELECTION>{});
       else if (wt == CC_RES_GROUP) walk(TypeC<CC_RES_GROUP>{});
-      else if (wt == CC_RES_VALUE) walk(TypeC<CC_RES_VALUE>{});
+      else if (!kBus && wt == CC_RES_VALUE) walk(TypeC<CC_RES_VALUE>{});
       else if (wt == CC_RES_TOPIC) walk(TypeC<CC_RES_TOPIC>{});
-      else walk(TypeC<0>{});
+      else if (!kBus || wt != CC_RES_BUS) walk(TypeC<0>{});
+      if constexpr (kBus) {
+        if (__any(b < e && type == CC_RES_BUS)) walk(TypeC<CC_RES_BUS>{});
+      }
 #ifdef CC_PHASE_TIMING
       ev_total_lane += lane_n;
 #endif
@@ -1039,9 +1232,9 @@ __global__ __launch_bounds__(kCT2, 3) void k_apply_coord(const XRec* __restrict_
   if (w == 0 && blockIdx.x < 4096) atomicAdd(&g_wg_t[4 * blockIdx.x + 3], (unsigned long long)ev_total_lane);
 #endif
   if (w == 0) {
-    E.store();
+    if (!kBus || type != CC_RES_BUS) E.store();  // (a bus's entries are only ever accessed in the block itself)
     CoordHdr* hp = reinterpret_cast<CoordHdr*>((uintptr_t)E.glb - sizeof(CoordHdr));  // (= blk)
-    if (type == CC_RES_TOPIC) {  // the snapshot offset and its flag live for one launch (kCoSnap)
+    if (type == CC_RES_TOPIC || (kBus && type == CC_RES_BUS)) {  // the snapshot offset and its flag live for one launch (kCoSnap)
       h.who = 0;
       h.flags &= ~kCoSnap;
     }
@@ -1076,7 +1269,7 @@ __global__ void k_clock_advance(const uint64_t* __restrict__ time, uint64_t n, u
 int launch_apply_coord(const CoordArgs& a, hipStream_t st) {
   if (a.tiles == 0) return 0;
   a.mark(K_APPLY_COORD, 1, st);
-  hipLaunchKernelGGL(k_apply_coord, dim3(a.sb_val * kQPerSb), dim3(kCT2), 0, st, a.xrec,
+  hipLaunchKernelGGL(a.bus ? k_apply_coord<true> : k_apply_coord<false>, dim3(a.sb_val * kQPerSb), dim3(kCT2), 0, st, a.xrec,
                      a.ttab, a.tiles, a.sb, a.sbq_base, a.sb_kind, a.res_type, a.inst_id, a.coord, a.coord_cap, a.val_meta, a.val_v, a.rst_status,
                      a.rst_value, a.ev_cnt, a.arena, a.arena_n, a.arena_cap, a.leak, a.leak_n, a.leak_cap, a.fx, a.err);
   a.mark(K_APPLY_COORD, 0, st);

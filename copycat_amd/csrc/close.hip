@@ -14,6 +14,9 @@
 //                      index); any other session: its listener entry is removed;
 //   MembershipGroupState.close :36-42 — members.remove(id) and "leave"(id) to every remaining member, even when
 //                      the session was not a member;
+//   TopicState.close :35-37 — listeners.remove(id), no event;
+//   MessageBusState.close :35-40 — members.remove(id) (its registrations stay in `topics`) and "leave"(id) to every
+//                      remaining member, even when the session was not a member;
 //   LockState / MapState — no close handler (A11): nothing.
 //
 // engine.hip turns the closing client sessions into the ordered list of instance slots (client order, then the
@@ -144,6 +147,29 @@ __global__ void k_close_apply(const uint32_t* __restrict__ cinst, const uint32_t
         for (uint32_t j = lo + 1; j < h.n; ++j) E[j - 1] = E[j];
         --h.n;
       }
+    } else if (type == CC_RES_BUS) {  // MessageBusState.close :35-40 (members sorted by instance id, common.h)
+      uint32_t lo = 0, hi = h.n;
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (E[mid].x < iid) lo = mid + 1; else hi = mid;
+      }
+      if (lo < h.n && E[lo].x == iid) {  // members.remove without clean(): the Join stays in the log unless delete() cleaned it
+        if (!(E[lo].idx & kBusCleaned)) {
+          const unsigned long long a = atomicAdd(leak_n, 1ull);
+          if (a < leak_cap) {
+            leak[a].idx = E[lo].idx;
+            leak[a].slot = r;
+            leak[a].pad = 0;
+          } else {
+            atomicOr(err, kErrCapacity);
+          }
+        }
+        for (uint32_t j = lo + 1; j < h.n; ++j) E[j - 1] = E[j];
+        --h.n;
+      }
+      // the session's registrations stay in `topics` (still retained, never reported by a later join); "leave"(id) to
+      // every remaining member, whether or not the closed session was one
+      for (uint32_t i = 0; i < h.n; ++i) ev(E[i].inst, CC_EV_BUS_LEAVE, iid);
     }
     cnt[p] = nev;
   }

@@ -136,6 +136,9 @@ constexpr int kPhases = 8;
 #endif
 
 // ---- ops registered per resource type (ResourceStateMachine.init + Copycat reflection configure) -----
+// (kBus = false: the table without MessageBusState, for the k_apply_coord instantiation of engines that hold no bus,
+// whose code is then the same as before the bus existed; apply_coord.hip)
+template <bool kBus = true>
 __host__ __device__ inline bool op_registered(uint32_t type, uint32_t op) {
   if (op == CC_OP_DELETE) return type != CC_RES_NONE;
   switch (type) {
@@ -148,6 +151,7 @@ __host__ __device__ inline bool op_registered(uint32_t type, uint32_t op) {
     case CC_RES_QUEUE: return op >= 90 && op <= 99;
     case CC_RES_MULTIMAP: return op == 75 || (op >= 78 && op <= 84);  // MultiMapState.java:37-207 (no 76 / 77)
     case CC_RES_TOPIC: return op >= 125 && op <= 127;  // TopicCommands.java:53,64,80
+    case CC_RES_BUS: return kBus && op >= 85 && op <= 88;  // MessageBusCommands.java (89 is ConsumerInfo, not an op)
   }
   return false;
 }
@@ -203,6 +207,7 @@ __host__ __device__ inline bool op_on_gpu(uint32_t type, uint32_t op) {
   if (type == CC_RES_LOCK || type == CC_RES_ELECTION) return op_registered(type, op);
   if (type == CC_RES_GROUP) return op_registered(type, op);  // schedule rows are batch barriers (engine.hip)
   if (type == CC_RES_TOPIC) return op_registered(type, op);  // publish: k_apply_coord + k_topic_fanout
+  if (type == CC_RES_BUS) return op_registered(type, op);    // fan-outs: k_apply_coord + k_topic_fanout
   return false;
 }
 
@@ -278,8 +283,33 @@ __host__ __device__ inline bool adds_entry(uint8_t type, uint8_t op, uint64_t au
     case CC_RES_VALUE: return op == CC_OP_VALUE_LISTEN;
     case CC_RES_QUEUE: return op == CC_OP_QUEUE_ADD || op == CC_OP_QUEUE_OFFER;
     case CC_RES_TOPIC: return op == CC_OP_TOPIC_LISTEN;
+    case CC_RES_BUS: return op == CC_OP_BUS_JOIN || op == CC_OP_BUS_REGISTER;  // (conservative: a re-join adds nothing)
     default: return false;
   }
+}
+// MessageBusState block (apply_coord.hip, case CC_RES_BUS): CoordHdr.n members sorted by instance id in entries
+// [0, n) (x = instance id, idx = Join index | kBusCleaned, inst = instance slot, pad = address handle) and CoordHdr.head
+// registrations sorted by (topic, instance id) from the back: registration j sits in entry cap - 1 - j (x = instance
+// id, 0 for the marker of a topic whose registration map is empty; pad = topic handle; idx = Register index).
+// n + head <= cap.  Handles are below 2^CC_BUS_HANDLE_BITS, which is what lets one sit in CoordEnt.pad.
+constexpr uint64_t kBusCleaned = 1ull << 63;  // in a member's idx: delete() cleaned its Join commit (the member stays)
+constexpr uint32_t kBusEvMax = 0xFFFFu;       // a commit's event count is 16 bits (ev_cnt, EvRec.k)
+// may a bus of `members` and `regs` exist?  max(members, 2) x regs bounds a leave's events (registrations of the
+// leaver x remaining members), a join's result rows (at most 2 x regs) and a register's events
+__host__ __device__ inline bool bus_product_ok(uint32_t members, uint32_t regs) {
+  return (uint64_t)(members < 2 ? 2 : members) * regs <= kBusEvMax;
+}
+// The entry count the prefix applies start a block from (host_path.hip, prefix_scan.hip): CoordHdr.n for every type
+// but a bus, whose block holds n + head entries.  Near the product bound a bus counts as fuller than it is, so that no
+// more adding rows pass in one part than the bound admits whichever of them are joins and which registers:
+// k adding rows leave at most (max(n, 2) + k) x (head + k).
+__host__ __device__ inline uint32_t coord_used(uint32_t type, uint32_t n, uint32_t head, uint32_t cap) {
+  if (type != CC_RES_BUS) return n;
+  const uint32_t used = n + head < cap ? n + head : cap, m = n < 2 ? 2 : n;
+  if ((uint64_t)(m + cap) * (head + cap) <= kBusEvMax) return used;  // (always at coord_cap <= 64)
+  uint32_t k = 0;
+  while (k < cap - used && (uint64_t)(m + k + 1) * (head + k + 1) <= kBusEvMax) ++k;
+  return cap - k;
 }
 // One staged record of the extended partition (map, set, multimap, coordination and value-event commits), one
 // 48-byte record per staging position: a bucket's run is then one contiguous span per chunk (its cache lines are
@@ -348,14 +378,20 @@ struct EvRec {
 // walk writes ev_cnt[g] = n and this record; the expansion kernel writes the n EvRecs {g, log[snap + i], payload,
 // k = i, CC_EV_MESSAGE, tag, CC_EVSRC_COMMIT}.  log = the sub-batch's listener log: the instance slots of the topic's
 // listeners (ascending instance id) as they stood at the publish row.
+// MessageBusState's register / unregister / leave fan-outs (MessageBusState.java:84-86,112-114,134-136) are the same
+// records with another event code; a leave leaves one record per topic of the leaver, whose emission indices run on
+// from record to record (k = first + i).
 struct FanRec {
   uint32_t g;       // staging position of the publish commit
   uint32_t n;       // listeners at that row (> 0: a publish to nobody leaves no record)
   uint64_t payload; // the canonical message (0 for NULL)
   uint32_t snap;    // first word of the listeners' snapshot in the listener log
-  uint32_t tag;     // the message's tag
+  uint32_t tag;     // the message's tag | event code << 8 | emission index of the record's first event << 16
 };
 static_assert(sizeof(FanRec) == 24, "FanRec is three 8-byte words");
+__host__ __device__ inline uint32_t fan_tag(uint32_t tag, uint32_t code, uint32_t first) {
+  return (tag & 0xFFu) | ((code & 0xFFu) << 8) | (first << 16);
+}
 // The sub-batch's fan records and listener log (device memory; the counters are zeroed per sub-batch).  A snapshot of
 // n words is always followed by a publish of n events, and a record stands for at least one event, so neither list
 // holds more entries than the sub-batch has events: both are sized like the event arena (cap), and one that overflows

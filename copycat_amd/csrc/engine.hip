@@ -202,7 +202,7 @@ static int ensure_ext(cc_engine* e, bool coord) {
 
 static bool is_coord(uint32_t type) {
   return type == CC_RES_LOCK || type == CC_RES_ELECTION || type == CC_RES_GROUP || type == CC_RES_QUEUE ||
-         type == CC_RES_TOPIC;
+         type == CC_RES_TOPIC || type == CC_RES_BUS;
 }
 
 extern "C" int cc_abi_version(void) { return CC_ABI_VERSION; }
@@ -573,10 +573,10 @@ int cc::dev_flush(cc_engine* e) {
 
 int cc::create_range(cc_engine* e, uint32_t first, uint32_t count, uint32_t type) {
   if (is_keyed(type) && !e->map_bits) return set_err(CC_ERR_CAPACITY, "map and set resources need cc_config.map_capacity > 0");
-  if (type < CC_RES_VALUE || type > CC_RES_TOPIC) return set_err(CC_ERR_INVALID, "unknown resource type");
+  if (type < CC_RES_VALUE || type > CC_RES_BUS) return set_err(CC_ERR_INVALID, "unknown resource type");
   if (type == CC_RES_SET) e->has_sets = true;
   if (type == CC_RES_VALUE) e->has_values = true;
-  if (type == CC_RES_TOPIC) e->has_topics = true;
+  if (type == CC_RES_TOPIC || type == CC_RES_BUS) e->has_topics = true;
   if (type == CC_RES_MULTIMAP) {
     e->has_mmaps = true;
     int rc = ensure_leak(e, kLeakCap);
@@ -593,6 +593,7 @@ int cc::create_range(cc_engine* e, uint32_t first, uint32_t count, uint32_t type
   if (is_coord(type) && (rc = ensure_ext(e, true))) return rc;
   for (uint64_t s = first; s < end; ++s) {
     e->res_type[s] = (uint8_t)type;
+    if (type == CC_RES_BUS) ++e->bus_slots;
     if (is_coord(type) || (type == CC_RES_VALUE && value_events)) e->sb_kind[s >> kSbShift] = 1;
     e->res_has_key[s] = 0;
     e->res_zombie[s] = 0;
@@ -694,6 +695,7 @@ int cc::delete_slot(cc_engine* e, uint32_t slot) {
   }
   if (e->map_bits) dev_fill(e, e->d_msmall, slot, 0, 1);  // no more small-map events for it
   e->res_type[slot] = CC_RES_NONE;
+  if (old_type == CC_RES_BUS) --e->bus_slots;
   // ResourceManagerStateMachineExecutor.close cancels the resource's timers
   e->gtimers.erase(std::remove_if(e->gtimers.begin(), e->gtimers.end(),
                                   [slot](const cc_engine::GroupTimer& g) { return g.slot == slot; }),
@@ -911,7 +913,7 @@ static int sessions_close_core(cc_engine* e, const std::vector<std::pair<uint64_
     HIPCHECK(hipStreamSynchronize(st));
     return CC_OK;
   }
-  // positions grouped by resource (only state machines with a close handler: value, election, group, topic)
+  // positions grouped by resource (only state machines with a close handler: value, election, group, topic, bus)
   std::vector<uint32_t> cinst(m), rlist, rstart, items;
   std::vector<std::pair<uint32_t, uint32_t>> rp;
   for (uint32_t p = 0; p < m; ++p) {
@@ -920,7 +922,8 @@ static int sessions_close_core(cc_engine* e, const std::vector<std::pair<uint64_
     const uint8_t ty = e->res_type[r];
     // a resource a failed deleteResource left behind is not in `resources` any more: no close handler (:253-257)
     if (e->res_zombie[r]) continue;
-    if (ty == CC_RES_VALUE || ty == CC_RES_ELECTION || ty == CC_RES_GROUP || ty == CC_RES_TOPIC) rp.emplace_back(r, p);
+    if (ty == CC_RES_VALUE || ty == CC_RES_ELECTION || ty == CC_RES_GROUP || ty == CC_RES_TOPIC || ty == CC_RES_BUS)
+      rp.emplace_back(r, p);
   }
   std::sort(rp.begin(), rp.end());
   for (size_t q = 0; q < rp.size(); ++q) {
@@ -1259,6 +1262,38 @@ extern "C" int cc_read_topic_listeners(cc_engine* e, uint32_t slot, uint64_t cap
   return CC_OK;
 }
 
+extern "C" int cc_read_bus_members(cc_engine* e, uint32_t slot, uint64_t cap, uint64_t* count, uint64_t* h_ids,
+                                   uint64_t* h_addr, uint64_t* h_index, uint8_t* h_cleaned) {
+  CoordHdr h;
+  std::vector<CoordEnt> q;
+  int rc = read_block(e, slot, CC_RES_BUS, h, q, nullptr);
+  if (rc) return rc;
+  for (uint32_t i = 0; i < h.n && i < cap; ++i) {
+    if (h_ids) h_ids[i] = q[i].x;
+    if (h_addr) h_addr[i] = q[i].pad;
+    if (h_index) h_index[i] = q[i].idx & ~kBusCleaned;
+    if (h_cleaned) h_cleaned[i] = (q[i].idx & kBusCleaned) ? 1 : 0;
+  }
+  if (count) *count = h.n;
+  return CC_OK;
+}
+
+extern "C" int cc_read_bus_registrations(cc_engine* e, uint32_t slot, uint64_t cap, uint64_t* count, uint64_t* h_topic,
+                                         uint64_t* h_ids, uint64_t* h_index) {
+  CoordHdr h;
+  std::vector<CoordEnt> q;
+  int rc = read_block(e, slot, CC_RES_BUS, h, q, nullptr);
+  if (rc) return rc;
+  for (uint32_t j = 0; j < h.head && j < cap; ++j) {  // registration j sits in entry cap - 1 - j (common.h)
+    const CoordEnt& x = q[e->coord_cap - 1 - j];
+    if (h_topic) h_topic[j] = x.pad;
+    if (h_ids) h_ids[j] = x.x;
+    if (h_index) h_index[j] = x.idx;
+  }
+  if (count) *count = h.head;
+  return CC_OK;
+}
+
 // Every commit the slot's state machine holds without having clean()ed it, ascending (the
 // oracle's orc_read_retained restates the same sites).
 extern "C" int cc_read_retained(cc_engine* e, uint32_t slot, uint64_t cap, uint64_t* count, uint64_t* h_index) {
@@ -1321,6 +1356,14 @@ extern "C" int cc_read_retained(cc_engine* e, uint32_t slot, uint64_t cap, uint6
       break;
     case CC_RES_TOPIC:  // the listeners' Listen commits (TopicState :42-62) + the ones close dropped (:35-37, leak lists)
       for (uint32_t i = 0; i < h.n; ++i) v.push_back(q[i].idx);
+      break;
+    case CC_RES_BUS:  // members' Joins unless delete() cleaned them + every registration's Register (MessageBusState
+                      // :45-151); replaced Joins / Registers, registrations a leave dropped, Joins a close dropped and
+                      // every Unregister: the leak lists
+      for (uint32_t i = 0; i < h.n; ++i)
+        if (!(q[i].idx & kBusCleaned)) v.push_back(q[i].idx);
+      for (uint32_t j = 0; j < h.head; ++j)
+        if (q[e->coord_cap - 1 - j].x) v.push_back(q[e->coord_cap - 1 - j].idx);
       break;
     case CC_RES_QUEUE:  // elements, less the head element() clean()ed (QueueState :51-199)
       for (uint32_t i = 0; i < h.n; ++i) {
@@ -1796,7 +1839,8 @@ extern "C" int cc_snapshot_restore(cc_engine* e, const void* h_buf, uint64_t siz
   e->has_values = e->has_values || std::find(e->res_type.begin(), e->res_type.end(), (uint8_t)CC_RES_VALUE) != e->res_type.end();
   e->has_mmaps = std::find(e->res_type.begin(), e->res_type.end(), (uint8_t)CC_RES_MULTIMAP) != e->res_type.end();
   if (e->has_mmaps && (rc = ensure_leak(e, kLeakCap))) return rc;
-  e->has_topics = std::find(e->res_type.begin(), e->res_type.end(), (uint8_t)CC_RES_TOPIC) != e->res_type.end();
+  e->bus_slots = (uint64_t)std::count(e->res_type.begin(), e->res_type.end(), (uint8_t)CC_RES_BUS);
+  e->has_topics = e->bus_slots || std::find(e->res_type.begin(), e->res_type.end(), (uint8_t)CC_RES_TOPIC) != e->res_type.end();
   e->sessions = std::move(sessions);
   e->small_live = e->map_bits && !e->ttl_live;  // (the next sub-batch recounts the maps still small)
   if (e->map_bits)  // (no replay is pending here: the restored snapshot flags start with no exit marks)

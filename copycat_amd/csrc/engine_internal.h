@@ -558,6 +558,7 @@ struct CoordArgs {
   unsigned long long* leak_n;
   uint64_t leak_cap;
   FanCtx* fx;              // TopicState.publish fan records + listener log (device; common.h FanCtx)
+  bool bus;                // the engine holds a MessageBusState: the instantiation with the bus walk
   uint32_t* err;
   Marker mark;
 };

@@ -380,7 +380,9 @@ struct cc_engine {
   // TopicState.publish (common.h FanCtx): the fan records live in d_ev_bucket and the listener log in d_ev_perm, both
   // [arena_cap] and free between the coordination apply and the order pass that fills them (events.hip)
   FanCtx* d_fan = nullptr;
-  bool has_topics = false;  // a TopicState resource exists: the coordination apply is followed by k_topic_fanout
+  bool has_topics = false;  // a TopicState or MessageBusState resource exists: the coordination apply is followed by
+                            // k_topic_fanout
+  uint64_t bus_slots = 0;   // MessageBusState resources: every Unregister lands in the leak log (sized per batch)
   // commits dropped without clean() (LeakRec, common.h): the kernels' device log, drained into per-slot host lists
   LeakRec* d_leak = nullptr;
   unsigned long long* d_leak_n = nullptr;

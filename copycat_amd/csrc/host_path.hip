@@ -179,7 +179,7 @@ extern "C" int cc_apply_batch_host_events(cc_engine* e, const cc_batch* h_cols, 
 // it are not applied (their results are not written), so the host can act (a larger engine from a snapshot, or the
 // commit failed) and resume at that row.
 //   1. Rows that can add an entry (lock with a timeout != 0, election listen, group join, value listen, queue
-//      add / offer) are the only ones that can overflow.  Every resource they address starts with its block's entry
+//      add / offer, topic listen, bus join / register) are the only ones that can overflow.  Every resource they address starts with its block's entry
 //      count (one strided copy of the block headers), and one pass over the batch keeps an upper bound per resource
 //      (+1 per adding row; removals are not counted, so it never falls short).  The rows before the first adding
 //      row whose bound would pass coord_cap go as one call.
@@ -321,7 +321,7 @@ int prefix_flow(cc_engine* e, uint64_t n, bool ck, PrefixPath& p, uint64_t* h_ap
   auto entries = [&](uint32_t r, uint32_t* out) -> int {  // one block's current entry count (CoordHdr.n)
     CoordHdr hd{};
     HIPCHECK(hipMemcpy(&hd, e->d_coord + (uint64_t)r * blk, sizeof hd, hipMemcpyDeviceToHost));
-    *out = hd.n;
+    *out = coord_used(e->res_type[r], hd.n, hd.head, cap);  // (a bus: members + registrations, common.h)
     return CC_OK;
   };
   uint64_t pos = 0;  // rows [0, pos) applied
@@ -446,7 +446,8 @@ struct HostPrefix : PrefixPath {
                            hdr.size(), hipMemcpyDeviceToHost));
       for (uint64_t k = 0; k < n; ++k) {
         const uint32_t r = res_of(k);
-        if (adds(k, r) && !bound.count(r)) bound[r] = hdr[r - rlo].n;
+        if (adds(k, r) && !bound.count(r))
+          bound[r] = coord_used(e->res_type[r], hdr[r - rlo].n, hdr[r - rlo].head, e->coord_cap);
       }
     }
     bounded = true;

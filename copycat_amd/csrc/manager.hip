@@ -23,7 +23,7 @@ using namespace cc;
 
 namespace {
 
-bool coord_type(uint32_t t) { return t == CC_RES_LOCK || t == CC_RES_ELECTION || t == CC_RES_GROUP || t == CC_RES_QUEUE || t == CC_RES_TOPIC; }
+bool coord_type(uint32_t t) { return t == CC_RES_LOCK || t == CC_RES_ELECTION || t == CC_RES_GROUP || t == CC_RES_QUEUE || t == CC_RES_TOPIC || t == CC_RES_BUS; }
 
 // every used slot of 64-slot group g holds `type`
 bool group_holds_only(const cc_engine* e, uint32_t g, uint32_t type) {
@@ -86,7 +86,7 @@ int instance_room(cc_engine* e, uint64_t index) {
 
 // A new key: resource id = commit index, a fresh state machine of `type` (:84-100,155-176).
 int new_resource(cc_engine* e, uint64_t key, uint32_t type, uint64_t index, uint32_t* rslot) {
-  if (type < CC_RES_VALUE || type > CC_RES_TOPIC) return set_err(CC_ERR_INVALID, "unknown resource type");
+  if (type < CC_RES_VALUE || type > CC_RES_BUS) return set_err(CC_ERR_INVALID, "unknown resource type");
   if (e->res_by_id.count(index)) return set_err(CC_ERR_INVALID, "resource id (commit index) already in use");
   uint32_t s = 0;
   int rc = alloc_res_slot(e, type, &s);

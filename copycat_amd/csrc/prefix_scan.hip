@@ -4,8 +4,9 @@
 // overflow a coordination collection (host_path.hip).  With the columns in HBM that walk is these kernels: they find,
 // without copying a column to the host, the first row in log order of [lo, hi) that
 //   * adds an entry (adds_entry, common.h: lock with a timeout != 0, election listen, group join, value listen,
-//     queue add / offer, topic listen; a row whose instance slot is out of range or unbound never counts), and
-//   * meets its resource's block full: CoordHdr.n + the adding rows for that resource before it in [lo, hi) equals
+//     queue add / offer, topic listen, bus join / register; a row whose instance slot is out of range or unbound never counts), and
+//   * meets its resource's block full: its entry count (coord_used, common.h: CoordHdr.n, a bus's members +
+//     registrations) + the adding rows for that resource before it in [lo, hi) equals
 //     coord_cap.
 // Removals are not counted, as on the host: the row is an upper bound's stop, and the driver reads the block's exact
 // count once the rows before it have applied.
@@ -77,7 +78,8 @@ __global__ __launch_bounds__(kPxBlock) void k_px_pick(PxArgs a) {
   if (r >= a.slots) return;
   const uint32_t c = a.cnt[r];
   if (!c) return;
-  const uint32_t n = ((const CoordHdr*)(a.coord + (size_t)r * coord_block(a.coord_cap)))->n;
+  const CoordHdr* hd = (const CoordHdr*)(a.coord + (size_t)r * coord_block(a.coord_cap));
+  const uint32_t n = coord_used(a.res_type[r], hd->n, hd->head, a.coord_cap);  // (a bus: members + registrations)
   uint32_t sel = 0;
   if ((uint64_t)n + c > a.coord_cap) {  // (each slot is listed at most once: the list holds `slots` entries)
     const uint32_t k = atomicAdd(a.list_n, 1u);

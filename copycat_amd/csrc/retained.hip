@@ -5,7 +5,8 @@
 // (MapState.java:89-228: replaced, removed and expired entries are cleaned), LockState holder unless delete() cleaned
 // it + waiters whose timeout has not fired (LockState.java:41-98), LeaderElectionState leader + listeners
 // (LeaderElectionState.java:35-108), MembershipGroupState members (MembershipGroupState.java:47-81), QueueState
-// elements less a head element() cleaned (QueueState.java:51-199); the host adds pending group schedules and the
+// elements less a head element() cleaned (QueueState.java:51-199), TopicState listeners, MessageBusState members unless
+// delete() cleaned them + registrations (MessageBusState.java:45-151); the host adds pending group schedules and the
 // commits dropped without clean() (leak lists; ResourceManagerCommit.clean :79-81 is never called for them).
 #include "common.h"
 #include "engine_internal.h"
@@ -44,7 +45,7 @@ __global__ void k_ret_coord(const uint8_t* __restrict__ res_type, const uint8_t*
   if (s >= slots) return;
   const uint32_t type = res_type[s];
   if (type != CC_RES_VALUE && type != CC_RES_LOCK && type != CC_RES_ELECTION && type != CC_RES_GROUP && type != CC_RES_QUEUE &&
-      type != CC_RES_TOPIC)
+      type != CC_RES_TOPIC && type != CC_RES_BUS)
     return;
   const uint8_t* blk = coord + (uint64_t)s * coord_block(ccap);
   const CoordHdr h = *reinterpret_cast<const CoordHdr*>(blk);
@@ -53,8 +54,12 @@ __global__ void k_ret_coord(const uint8_t* __restrict__ res_type, const uint8_t*
   if (l == 0 && (type == CC_RES_LOCK || type == CC_RES_ELECTION) && (h.flags & kCoHeld) && !(h.flags & kCoCleaned))
     ret_mark(h.idx, first, count, bm);  // the holder / leader commit
   const bool ring = type == CC_RES_LOCK || type == CC_RES_QUEUE;
+  if (type == CC_RES_BUS)  // the registrations' Register commits, from the back of the block (common.h); x = 0: a marker
+    for (uint32_t j = l; j < h.head && j < ccap; j += kWave)
+      if (q[ccap - 1 - j].x) ret_mark(q[ccap - 1 - j].idx, first, count, bm);
   for (uint32_t i = l; i < h.n && i < ccap; i += kWave) {
     const CoordEnt& x = q[ring ? ((h.head + i) & (ccap - 1)) : i];
+    if (type == CC_RES_BUS && (x.idx & kBusCleaned)) continue;              // delete() cleaned the member's Join
     if (type == CC_RES_LOCK && x.x != kNoDeadline && x.x <= clk) continue;  // tryLock timeout fired: cleaned
     if (type == CC_RES_QUEUE && (x.pad & kQCleaned)) continue;            // head element() cleaned in place
     ret_mark(x.idx, first, count, bm);

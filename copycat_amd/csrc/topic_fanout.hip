@@ -5,9 +5,15 @@
 // they stood at that row lie in the sub-batch's listener log (a snapshot shared by every publish between two changes
 // of the list).  k_topic_fanout, launched after the coordination apply and before the order pass (events.hip), writes
 // the n events of every record into the sub-batch's event arena:
-//   EvRec{g, target = log[snap + i], payload, k = i, CC_EV_MESSAGE, tag, CC_EVSRC_COMMIT},  i = 0 .. n - 1,
+//   EvRec{g, target = log[snap + i], payload, k = first + i, code, tag, CC_EVSRC_COMMIT},  i = 0 .. n - 1,
+// with the code and `first` from the record (FanRec.tag; a topic's records carry CC_EV_MESSAGE and 0),
 // i.e. in ascending listener instance id (engine-defined: each event of one publish goes to a different session).  The
 // order pass then sees only real events, each with its (g, k) and a matching ev_cnt.
+//
+// MessageBusState's register / unregister / leave (MessageBusState.java:84-86,112-114,134-136) publish a
+// ConsumerInfo(topic, address) to every member of the bus: the same records with CC_EV_BUS_REGISTER / _UNREGISTER, the
+// payload topic << 32 | address, against a snapshot of the members.  A leave leaves one record per topic of the leaver
+// for the same commit g; `first` runs on across them (0, n, 2n, ...), so the commit's emission indices are dense.
 //
 // A workgroup takes kFT records at a time: a scan of their n, one arena reservation for all their events (never one
 // per event), then (record, i) flattened over the lanes — lane e of a pass handles event e of the chunk, found by a
@@ -94,8 +100,10 @@ __global__ __launch_bounds__(kFT) void k_topic_fanout(const FanCtx* __restrict__
           const uint32_t target = lg[(uint64_t)rsnap[lo] + i];
           stage[3 * t + 0] = (uint64_t)rg[lo] | ((uint64_t)target << 32);
           stage[3 * t + 1] = rpay[lo];
-          stage[3 * t + 2] = (uint64_t)(i & 0xFFFFu) | ((uint64_t)CC_EV_MESSAGE << 16) | ((uint64_t)(rtag[lo] & 0xFFu) << 24) |
-                             ((uint64_t)CC_EVSRC_COMMIT << 32);
+          // FanRec.tag = tag | code << 8 | first emission index << 16 (a topic's: CC_EV_MESSAGE, 0)
+          const uint32_t tg = rtag[lo];
+          stage[3 * t + 2] = (uint64_t)((i + (tg >> 16)) & 0xFFFFu) | ((uint64_t)((tg >> 8) & 0xFFu) << 16) |
+                             ((uint64_t)(tg & 0xFFu) << 24) | ((uint64_t)CC_EVSRC_COMMIT << 32);
         }
         __syncthreads();
         // the pass's 3 * cnt words, contiguous in the arena from event base + e0

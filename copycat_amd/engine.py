@@ -76,6 +76,8 @@ def lib():
             "cc_read_election_state": (i32, [P, u32, P, P, u64, P, P, P]),
             "cc_read_group_members": (i32, [P, u32, u64, P, P]),
             "cc_read_topic_listeners": (i32, [P, u32, u64, P, P, P]),
+            "cc_read_bus_members": (i32, [P, u32, u64, P, P, P, P, P]),
+            "cc_read_bus_registrations": (i32, [P, u32, u64, P, P, P, P]),
             "cc_read_retained": (i32, [P, u32, u64, P, P]),
             "cc_retained_bitmap": (i32, [P, u64, u64, P, P]),
             "cc_advance_time": (i32, [P, u64]),
@@ -662,6 +664,22 @@ class Engine:
         _check(self.L.cc_read_topic_listeners(self.h, slot, cap, C.byref(n), _np(ids), _np(idx)))
         m = min(n.value, cap)
         return list(zip(ids[:m].tolist(), idx[:m].tolist()))
+
+    def read_bus_members(self, slot, cap=4096):
+        """[(member instance id, address handle, Join commit index, cleaned)], ascending by id (cc_read_bus_members)"""
+        ids, addr, idx = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+        cl, n = np.zeros(cap, np.uint8), C.c_uint64()
+        _check(self.L.cc_read_bus_members(self.h, slot, cap, C.byref(n), _np(ids), _np(addr), _np(idx), _np(cl)))
+        m = min(n.value, cap)
+        return list(zip(ids[:m].tolist(), addr[:m].tolist(), idx[:m].tolist(), cl[:m].astype(bool).tolist()))
+
+    def read_bus_registrations(self, slot, cap=4096):
+        """[(topic handle, registrant instance id, Register commit index)], ascending by (topic, id); a topic whose
+        registration map is empty is one row (topic, 0, 0) (cc_read_bus_registrations)"""
+        tp, ids, idx, n = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64), np.zeros(cap, np.uint64), C.c_uint64()
+        _check(self.L.cc_read_bus_registrations(self.h, slot, cap, C.byref(n), _np(tp), _np(ids), _np(idx)))
+        m = min(n.value, cap)
+        return list(zip(tp[:m].tolist(), ids[:m].tolist(), idx[:m].tolist()))
 
     def retained(self, slot):
         """Ascending log indices of every commit the slot's state machine still holds without having clean()ed it

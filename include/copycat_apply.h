@@ -56,6 +56,8 @@ extern "C" {
 #define CC_RES_QUEUE     7  /* QueueState        collections/.../state/QueueState.java:33 (a FIFO of CC_QUEUE_CAP) */
 #define CC_RES_MULTIMAP  8  /* MultiMapState     collections/.../state/MultiMapState.java:30 (shares the map table) */
 #define CC_RES_TOPIC     9  /* TopicState        coordination/.../state/TopicState.java:31 (listeners keyed by instance id) */
+#define CC_RES_BUS      10  /* MessageBusState   coordination/.../state/MessageBusState.java:30 (members keyed by instance id +
+                               topics -> registrations keyed by instance id, both in one coordination block) */
 #define CC_QUEUE_CAP    64
 
 /* ---- op codes = Catalyst @SerializeWith ids of the inner operation ------------- */
@@ -131,6 +133,14 @@ extern "C" {
 #define CC_OP_TOPIC_LISTEN     125
 #define CC_OP_TOPIC_UNLISTEN   126
 #define CC_OP_TOPIC_PUBLISH    127
+/* MessageBusCommands.java (Join: the member's address in operand a; Register / Unregister: the topic in operand a;
+ * both CC_TAG_HANDLE and below 2^CC_BUS_HANDLE_BITS, else the call fails with CC_ERR_UNSUPPORTED; 89 is ConsumerInfo,
+ * not an op) */
+#define CC_OP_BUS_JOIN         85
+#define CC_OP_BUS_LEAVE        86
+#define CC_OP_BUS_REGISTER     87
+#define CC_OP_BUS_UNREGISTER   88
+#define CC_BUS_HANDLE_BITS     32  /* a ConsumerInfo(topic, address) travels as one payload: topic << 32 | address */
 
 /* ---- canonical tagged values: Java equals == (tag, payload) equality ---------- */
 #define CC_TAG_NULL    0
@@ -140,6 +150,8 @@ extern "C" {
 #define CC_TAG_HANDLE  4   /* host-interned object (String, Runnable callback ...) */
 #define CC_TAG_SET     5   /* result only: Set<Long> of MembershipGroupState.join; payload = member count,
                               members are written to the aux-result stream */
+#define CC_TAG_MAP     7   /* result only: Map<String, Set<Address>> of MessageBusState.join; payload = topic count,
+                              the rows follow in the event stream (CC_EV_BUS_TOPIC / CC_EV_BUS_ADDRESS) */
 #define CC_TAG_LIST    6   /* result only: a Collection (MultiMapState get / remove(key)); payload = element count */
 
 /* flags column: bits 0-2 tag(a), bits 3-5 tag(b), bits 6-7 key tag (keys are never null,
@@ -178,6 +190,16 @@ extern "C" {
                              publish row, target = the listener's instance slot, src CC_EVSRC_COMMIT, tag / payload =
                              the canonical message (payload 0 for NULL); within one publish in ascending listener
                              instance id (engine-defined: each goes to a different session) */
+#define CC_EV_BUS_LEAVE      9  /* MessageBusState.close :35-40 "leave"(closed instance id, tag LONG) to every remaining
+                                  member, src CC_EVSRC_CLOSE, whether or not the closed instance was a member */
+#define CC_EV_BUS_REGISTER  10  /* "register"(ConsumerInfo) :112-114 to every member; tag HANDLE, payload = topic << 32 |
+                                  address of the registrant; src CC_EVSRC_COMMIT, ascending member instance id */
+#define CC_EV_BUS_UNREGISTER 11 /* "unregister"(ConsumerInfo) :84-86,134-136, same layout; a leave publishes one fan-out
+                                  per topic of the leaver, in ascending topic handle (engine-defined) */
+#define CC_EV_BUS_TOPIC     12  /* not an event: a row of a join's Map result (src CC_EVSRC_RESULT, target = the joiner):
+                                  payload = a topic handle, ascending; followed by its CC_EV_BUS_ADDRESS rows */
+#define CC_EV_BUS_ADDRESS   13  /* not an event: one distinct address of the topic row before it, ascending (none: an
+                                  empty set) */
 
 /* event source */
 #define CC_EVSRC_COMMIT 0  /* published while applying commit `pos` */
@@ -224,6 +246,9 @@ typedef struct cc_config {
 #define CC_VALUE_LISTENERS     64
 #define CC_TOPIC_LISTENERS     64  /* coord_cap listeners per topic; at coord_cap 65536 the limit is 65,535 (a commit's
                                       event count is 16 bits) */
+#define CC_BUS_ENTRIES         64  /* coord_cap entries per bus in all: members + registrations + empty-topic markers;
+                                      an entry is also refused when max(members, 2) x registrations would pass 65,535
+                                      (a commit's event count is 16 bits; binds only at coord_cap >= 512) */
 
 /* ---- one batch of committed entries, SoA, log order ------------------------------------------------
  * Row i is InstanceCommand/InstanceQuery{instance, op} of log entry index[i]
@@ -398,6 +423,14 @@ int  cc_read_group_members(cc_engine* e, uint32_t slot, uint64_t cap, uint64_t* 
  * index.  Exists from this commit on, under the unchanged CC_ABI_VERSION 6 (symbols are only added). */
 int  cc_read_topic_listeners(cc_engine* e, uint32_t slot, uint64_t cap, uint64_t* count, uint64_t* h_ids,
                              uint64_t* h_index);
+/* MessageBusState.members (MessageBusState.java:31): ascending instance id; each member's address handle, Join commit
+ * index and whether delete() cleaned that commit (:148: the member stays a member).  Any array may be NULL. */
+int  cc_read_bus_members(cc_engine* e, uint32_t slot, uint64_t cap, uint64_t* count, uint64_t* h_ids, uint64_t* h_addr,
+                         uint64_t* h_index, uint8_t* h_cleaned);
+/* MessageBusState.topics (:32): ascending (topic handle, instance id) with each Register commit index; a topic whose
+ * registration map is empty is one row with id 0 and index 0.  Both exist from this commit on, ABI version unchanged. */
+int  cc_read_bus_registrations(cc_engine* e, uint32_t slot, uint64_t cap, uint64_t* count, uint64_t* h_topic,
+                               uint64_t* h_ids, uint64_t* h_index);
 /* Log compaction for every state machine (Commit.clean()): the log indices of every commit
  * the slot's state machine still holds without having clean()ed it, ascending — *count of them, the first
  * min(cap, count) to h_index.  Value: `current` + listeners (AtomicValueState.java:41-157, needs
@@ -450,7 +483,8 @@ int  cc_sessions_expire_host(cc_engine* e, const uint64_t* h_bitmap, uint64_t se
 /* ---- per-kernel timing (HIP events recorded on the launch stream around every engine kernel) ----------
  * kernel ids: 0 k_part_tile, 1 k_apply_value, 2 k_unpermute, 3 k_apply_map, 4 k_map_hot (hot-key lists +
  * scan, apply_map_hot.hip), 5 k_apply_coord (coordination + value events), 6 k_events (event scan+scatter),
- * 7 k_topic_fanout (TopicState.publish expansion, topic_fanout.hip; launched only on engines that hold a topic). */
+ * 7 k_topic_fanout (TopicState.publish and MessageBusState register / unregister / leave expansion, topic_fanout.hip;
+ * launched only on engines that hold a topic or a bus). */
 #define CC_PROFILE_KERNELS 8
 int  cc_profile_enable(cc_engine* e, int on);
 int  cc_profile_reset(cc_engine* e);
