@@ -179,10 +179,11 @@ class BusWorld:
         self.inst[slot] = (res, iid, client)
         self.slot_of[iid] = slot
 
-    def close_client(self, client):
-        """the close fan-out's events [(target instance slot, code, tag, payload)], instances in ascending slot"""
+    def close_client(self, client, keep=()):
+        """the close fan-out's events [(target instance slot, code, tag, payload)], instances in ascending slot; the
+        slots in `keep` stay open (a close loop that an exception ended early leaves the client's later instances)"""
         ev = []
-        for s in sorted(s for s, (_, _, c) in self.inst.items() if c == client):
+        for s in sorted(s for s, (_, _, c) in self.inst.items() if c == client and s not in keep):
             res, iid, _ = self.inst.pop(s)
             del self.slot_of[iid]
             ev.extend((self.slot_of[t], c, g, p) for t, c, g, p in self.buses[res].close(iid))

@@ -13,6 +13,7 @@ import pytest
 from copycat_amd import abi
 from copycat_amd.batch import Batch, events_check, pack, pack_events, unpack_events, unpack_results
 from tests.bus_model import ILLEGAL_STATE, OK_MAP, OK_NULL, BusWorld, bus_rows, info
+from tests.coord_bus_cases import BusTopicRows
 from tests.test_bus_model import KATS
 from tests.test_gpu_topic import World as TopicTestWorld
 from tests.test_gpu_topic import _dev_prefix, _host_prefix
@@ -146,7 +147,7 @@ def test_kats(kat):
 
 
 # ---- 2. random parity -----------------------------------------------------------------------------------------------
-NB, CLIENTS, TOPICS, ADDRS = 48, 12, 6, 5
+NB, CLIENTS = 48, 12
 
 
 def _mixed_world(**cfg):
@@ -158,46 +159,23 @@ def _mixed_world(**cfg):
 
 def _mixed_stream(w, n, seed, index0=1, cap=64):
     """Random bus traffic (register / unregister heavy, with joins, leaves, a few Deletes and foreign ops) mixed with
-    topic, group and lock rows.  A scratch copy of the bus model walks the stream as it is drawn and turns a join or
-    register that would take a bus past cap - 2 entries into a leave, so the stream never fills a block."""
-    import copy
-
+    topic, group and lock rows.  The bus and topic rows are tests/coord_bus_cases.BusTopicRows's, whose scratch copy of
+    the bus model walks the stream as it is drawn and turns a join or register that would take a bus past cap - 2
+    entries into a leave, so the stream never fills a block."""
     rng = np.random.default_rng(seed)
     b = Batch(n)
     b.index[:] = np.arange(index0, index0 + n, dtype=np.uint64)
     b.time[:] = np.arange(index0, index0 + n, dtype=np.uint64)
-    binst = np.array([s for r, t in enumerate(w.types) if t == B for s in w.inst[r]], np.uint32)
-    other = {t: np.array([s for r, x in enumerate(w.types) if x == t for s in w.inst[r]], np.uint32) for t in (T, G, L)}
+    other = {t: np.array([s for r, x in enumerate(w.types) if x == t for s in w.inst[r]], np.uint32) for t in (G, L)}
     kind = rng.choice(4, n, p=[0.85, 0.05, 0.05, 0.05])
     u = rng.random(n)
-    scratch = copy.deepcopy(w.BW)
-    H = abi.cc_flags(abi.CC_TAG_HANDLE)
+    rows = BusTopicRows(w, rng, cap)
     for i in range(n):
         k, x = int(kind[i]), float(u[i])
         if k == 0:
-            s = int(binst[rng.integers(0, len(binst))])
-            if x < 0.10:
-                op, a = JOIN, 500 + int(rng.integers(0, ADDRS))
-            elif x < 0.16:
-                op, a = LEAVE, 0
-            elif x < 0.55:
-                op, a = REG, 1 + int(rng.integers(0, TOPICS))
-            elif x < 0.97:
-                op, a = UNREG, 1 + int(rng.integers(0, TOPICS))
-            elif x < 0.98:
-                op, a = DELETE, 0
-            else:
-                op, a = abi.CC_OP_TOPIC_PUBLISH, 0
-            r, iid, _ = scratch.inst[s]
-            if op in (JOIN, REG) and scratch.buses[r].entries() >= cap - 2:
-                op, a = LEAVE, 0
-            scratch.buses[r].apply(op, iid, int(b.index[i]), a)
-            b.inst[i], b.op[i], b.a[i] = s, op, a
-            b.flags[i] = H if op in (JOIN, REG, UNREG) else 0
+            rows.bus(b, i, x)
         elif k == 1:
-            b.inst[i] = other[T][rng.integers(0, len(other[T]))]
-            b.op[i] = abi.CC_OP_TOPIC_PUBLISH if x < 0.6 else (abi.CC_OP_TOPIC_LISTEN if x < 0.85 else abi.CC_OP_TOPIC_UNLISTEN)
-            b.flags[i], b.a[i] = abi.cc_flags(abi.CC_TAG_LONG), i
+            rows.topic(b, i, x)
         elif k == 2:
             b.inst[i] = other[G][rng.integers(0, len(other[G]))]
             b.op[i] = abi.CC_OP_GROUP_JOIN if x < 0.5 else abi.CC_OP_GROUP_LEAVE

@@ -29,8 +29,7 @@ class World:
     """An engine, the topic model and (for the other types) the oracle over one registry: resource r of types[r] has
     the instance slots inst[r], instance id iid(slot), client client(slot)."""
 
-    def __init__(self, types, K, iid=lambda s: 1000 + s, client=None, **cfg):
-        from copycat_amd.engine import Engine
+    def __init__(self, types, K, iid=lambda s: 1000 + s, client=None, flags=FLAGS, **cfg):
         from oracle.oracle_py import Oracle
 
         self.types = list(types)
@@ -39,10 +38,10 @@ class World:
         self.max_inst = sum(self.K) + 8
         cfg.setdefault("max_events", 1 << 20)
         self.cfg = dict(max_resources=len(types), max_instances=self.max_inst, max_batch=cfg.pop("max_batch", 1 << 17),
-                        flags=FLAGS, **cfg)
-        self.E = Engine(self.cfg["max_resources"], self.max_inst, self.cfg["max_batch"], flags=FLAGS, **cfg)
+                        flags=flags, **cfg)
+        self.E = self.fresh_engine()
         self.W = TopicWorld()
-        self.O = Oracle(len(types), self.max_inst, 1)
+        self.O = Oracle(len(types), self.max_inst, flags & abi.CC_CFG_TIMERS_DEFERRED)  # (the oracle's timer mode)
         self.inst, s = {}, 0
         for r, t in enumerate(self.types):
             self.inst[r] = list(range(s, s + self.K[r]))

@@ -95,8 +95,9 @@ class TopicWorld:
         self.inst[slot] = (res, iid, client)
         self.slot_of[iid] = slot
 
-    def close_client(self, client):
-        for s in sorted(s for s, (_, _, c) in self.inst.items() if c == client):
+    def close_client(self, client, keep=()):
+        """the slots in `keep` stay open (a close loop that an exception ended early leaves the client's later instances)"""
+        for s in sorted(s for s, (_, _, c) in self.inst.items() if c == client and s not in keep):
             res, iid, _ = self.inst.pop(s)
             del self.slot_of[iid]
             self.topics[res].close(iid)
