@@ -265,6 +265,18 @@ class cc_wire_out(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("inst", "iid", "op", "flags", "key", "a", "b", "aux", "kind")]
 
 
+# the GPU wire decoder (include/copycat_apply.h "the same decode on the GPU"; copycat_amd/csrc/wire_gpu.hip)
+CC_WIRE_TILE_ROWS = 2048
+
+
+class cc_wire_control(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("row", "kind", "key", "a", "b")]
+
+
+class cc_wire_stats(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("rows", "device_rows", "host_rows")]
+
+
 # packed host batches (include/copycat_apply.h "packed host batches"; copycat_amd/csrc/pack.cpp, unpack.hip)
 CC_PACK_BLOCK_ROWS = 4096
 CC_PACK_VERSION = 1

@@ -109,6 +109,11 @@ static void free_all(cc_engine* e) {
     if (p) (void)hipFree(p);
   for (void*& p : e->hw_buf)
     if (p) (void)hipFree(p), p = nullptr;
+  for (void*& p : e->wr_buf)
+    if (p) (void)hipFree(p), p = nullptr;
+  if (e->wr_pin) (void)hipHostFree(e->wr_pin);
+  for (hipEvent_t ev : e->wr_ev)
+    if (ev) (void)hipEventDestroy(ev);
   if (e->d_hh_key) (void)hipFree(e->d_hh_key);
   if (e->d_hh_val) (void)hipFree(e->d_hh_val);
   if (e->h_pin) (void)hipHostFree(e->h_pin);
@@ -721,6 +726,7 @@ int cc::delete_slot(cc_engine* e, uint32_t slot) {
     e->used_inst.clear(i);
     mark_dirty(e->inst_dirty_lo, e->inst_dirty_hi, i, i + 1);
   }
+  ++e->inst_gen;
   // ResourceManager.resources / keys / ResourceHolder.sessions
   auto rit = e->res_by_id.find(e->res_id[slot]);
   if (rit != e->res_by_id.end() && rit->second == slot) e->res_by_id.erase(rit);
@@ -752,6 +758,7 @@ int cc::open_range(cc_engine* e, uint32_t first, uint32_t count, uint32_t res_fi
     e->inst_by_id[id_first + k] = (uint32_t)(first + k);
     e->used_inst.set(first + k);
   }
+  ++e->inst_gen;
   mark_dirty(e->inst_dirty_lo, e->inst_dirty_hi, first, end);
   return CC_OK;
 }
@@ -1036,6 +1043,7 @@ static int sessions_close_core(cc_engine* e, const std::vector<std::pair<uint64_
     e->used_inst.clear(i);
     ++closed;
   }
+  ++e->inst_gen;
   if (h_closed) *h_closed = closed;
   return check_device_err(e);
 }
@@ -1807,6 +1815,7 @@ extern "C" int cc_snapshot_restore(cc_engine* e, const void* h_buf, uint64_t siz
   e->keys.clear();
   e->res_by_id.clear();
   e->inst_by_id.clear();
+  ++e->inst_gen;  // (the GPU wire decoder's id -> slot table is no part of a snapshot: rebuilt on its next call)
   e->used_res.reset(e->cfg.max_resources);
   e->used_inst.reset(e->cfg.max_instances);
   for (uint32_t s = 0; s < e->cfg.max_resources; ++s) {

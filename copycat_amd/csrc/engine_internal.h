@@ -783,4 +783,51 @@ struct EvpackArgs {
 };
 int launch_evpack(const EvpackArgs& a, hipStream_t st);
 
+// Wire bytes -> wide columns (wire_gpu.hip k_wire_decode): tile k decodes entries [CC_WIRE_TILE_ROWS k, ...) of the
+// staged segment.  Entry i is bytes[off[i] - off[0], off[i + 1] - off[0]); `bytes` is 16-byte aligned and padded so
+// that whole 16-byte loads up to the segment's rounded-up end stay inside it.  Plain entries (wire_plain.h) are
+// decoded; every other entry gets the host decoder's defaults and its bit in `esc` (bit i & 63 of word i >> 6).
+struct WireArgs {
+  const uint8_t* bytes;
+  const uint64_t* off;       // [n + 1], non-decreasing (the host checked)
+  uint64_t n;
+  cc_wire_codec codec;
+  const uint32_t* schema;    // [256] wire_plain.h schema words
+  const uint64_t* tbl_id;    // instance id -> slot, open addressing: [tbl_mask + 1] ids ...
+  const uint32_t* tbl_slot;  // ... and slots (~0: an empty cell)
+  uint32_t tbl_mask;
+  uint32_t max_inst;
+  uint32_t* inst;            // the columns, each 16-byte aligned
+  uint8_t* op;
+  uint8_t* flags;
+  uint64_t* key;
+  uint64_t* a;
+  uint64_t* b;
+  uint64_t* aux;
+  uint64_t* iid;             // may be null
+  uint64_t* esc;             // [ceil(n / 64)]
+  unsigned long long* esc_n; // escaped rows (zeroed by the caller)
+};
+int launch_wire_decode(const WireArgs& a, hipStream_t st);
+// one host-decoded row written over the device columns (k_wire_patch)
+struct WirePatch {
+  uint64_t row, iid, key, a, b, aux;
+  uint32_t inst;
+  uint8_t op, flags, pad0, pad1;
+};
+static_assert(sizeof(WirePatch) == 56, "WirePatch");
+int launch_wire_patch(const WireArgs& a, const WirePatch* rows, uint64_t m, hipStream_t st);
+inline uint32_t wire_tbl_hash(uint64_t id, uint32_t mask) { return (uint32_t)((id * 0x9E3779B97F4A7C15ull) >> 32) & mask; }
+// wire.cpp: the host decoder of one entry (reported as `row`, written to index `at` of `out`), and the registration of
+// the String keys among `keys` (cc_handle_hashes), as cc_wire_decode does it
+int wire_decode_one(cc_engine* e, const cc_wire_codec& c, cc_wire_interner* in, const uint8_t* p, const uint8_t* end,
+                    uint64_t row, uint64_t at, const cc_wire_out* out);
+int wire_register_keys(cc_engine* e, cc_wire_interner* in, const uint64_t* keys, uint64_t m);
+// The decode behind cc_wire_decode_to_device and cc_apply_wire_host (wire_gpu.hip).  stop_at_ctl: the fallback stops
+// at the first manager entry (row *stop_row, else n): rows after it are neither interned nor checked.
+int wire_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* in, const uint8_t* h_buf, uint64_t buf_len,
+                   const uint64_t* h_offsets, uint64_t n, const cc_batch_out* d_cols, uint64_t* d_iid,
+                   cc_wire_control* h_ctl, uint64_t ctl_cap, uint64_t* ctl_count, cc_wire_stats* stats, hipStream_t st,
+                   uint64_t* bad_row, bool stop_at_ctl, uint64_t* stop_row);
+
 }  // namespace cc

@@ -431,6 +431,15 @@ struct cc_engine {
   std::vector<hipEvent_t> ep_stamp, ep_call_stamp;
   uint64_t ep_chunks = 0;
   uint64_t* ep_pin = nullptr;
+  // The GPU wire decoder (wire_gpu.hip).  inst_gen moves whenever inst_by_id changes (open, close, delete, snapshot
+  // restore); the decoder rebuilds its device table (instance id -> slot; not part of a snapshot) when wr_gen differs.
+  uint64_t inst_gen = 1, wr_gen = 0;
+  uint32_t wr_mask = 0;
+  void* wr_buf[6] = {};  // staged bytes, offsets, escape bitmap + count, table, schema words, patch rows
+  size_t wr_cap[6] = {};
+  uint64_t* wr_pin = nullptr;  // pinned: the escape count
+  hipEvent_t wr_ev[4] = {};    // the last decode's stages (cc_wire_timeline): before the H2D, the kernel, the escape
+  bool wr_timed = false;       // read-back, and after it
   // per-kernel profiling (cc_profile_enable)
   bool prof_on = false;
   std::vector<hipEvent_t> ev_pool;

@@ -107,6 +107,8 @@ int hw_events_back(cc_engine* e, const cc_events* h, const cc_events* d) {
   return set_err(CC_ERR_CAPACITY, "more events than the host event stream holds");
 }
 
+int apply_staged(cc_engine* e, void* const* dcol, uint64_t n, const cc_results* hout, const cc_events* hev, cc_events& dev);
+
 int apply_host(cc_engine* e, const cc_batch* h, uint64_t n, const cc_results* hout, const cc_events* hev) {
   if (!e || !h || !hout || (n && (!hout->status || !hout->value))) return set_err(CC_ERR_INVALID, "null argument");
   HIPCHECK(hipSetDevice(e->device));
@@ -129,6 +131,13 @@ int apply_host(cc_engine* e, const cc_batch* h, uint64_t n, const cc_results* ho
     if ((rc = hw(e, kHwCol + c, esz[c] * n, &dcol[c]))) return rc;
     HIPCHECK(hipMemcpyAsync(dcol[c], src[c], esz[c] * n, hipMemcpyHostToDevice, st));
   }
+  return apply_staged(e, dcol, n, hout, hev, dev);
+}
+
+// the rest of apply_host, on staged device columns (also cc_apply_wire_host's, whose columns the GPU decoder wrote)
+int apply_staged(cc_engine* e, void* const* dcol, uint64_t n, const cc_results* hout, const cc_events* hev, cc_events& dev) {
+  hipStream_t st = e->own_stream;
+  int rc;
   void *d_status, *d_value;
   if ((rc = hw(e, kHwStatus, n, &d_status)) || (rc = hw(e, kHwValue, 8 * n, &d_value))) return rc;
   // sentinel prefill: status 0xFF is no legal status (tag nibble 15), so a row the kernels never wrote comes back as
@@ -159,6 +168,45 @@ int apply_host(cc_engine* e, const cc_batch* h, uint64_t n, const cc_results* ho
 }
 
 }  // namespace
+
+// The log segment itself: decoded on the GPU into the staging columns (wire_gpu.hip), rows before the first manager
+// entry applied.
+extern "C" int cc_apply_wire_host(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* in, const uint8_t* h_buf,
+                                  uint64_t buf_len, const uint64_t* h_offsets, uint64_t n, const uint64_t* h_index,
+                                  const uint64_t* h_time, const cc_results* hout, const cc_events* hev,
+                                  uint64_t* h_applied, cc_wire_control* ctl) {
+  if (!e || !hout || !h_applied || !ctl || (n && (!hout->status || !hout->value || !h_index)))
+    return set_err(CC_ERR_INVALID, "null argument");
+  *h_applied = 0;
+  HIPCHECK(hipSetDevice(e->device));
+  e->last_err_bits = 0;
+  hipStream_t st = e->own_stream;
+  if (st != e->last_stream) HIPCHECK(hipStreamSynchronize(e->last_stream));
+  e->last_stream = st;
+  const size_t esz[9] = {8, 8, 4, 1, 1, 8, 8, 8, 8};
+  void* dcol[9] = {};
+  uint64_t r = 0;
+  if (n) {
+    for (int c = 0; c < 9; ++c)
+      if (c != 1 || h_time) TRY(hw(e, kHwCol + c, esz[c] * n, &dcol[c]));
+    const cc_batch_out cols{nullptr, nullptr, (uint32_t*)dcol[2], (uint8_t*)dcol[3], (uint8_t*)dcol[4],
+                            (uint64_t*)dcol[5], (uint64_t*)dcol[6], (uint64_t*)dcol[7], (uint64_t*)dcol[8]};
+    uint64_t nctl = 0;
+    TRY(wire_to_device(e, codec, in, h_buf, buf_len, h_offsets, n, &cols, nullptr, ctl, 1, &nctl, nullptr, st, nullptr,
+                       true, &r));
+    if (r) HIPCHECK(hipMemcpyAsync(dcol[0], h_index, 8 * r, hipMemcpyHostToDevice, st));
+    if (r && h_time) HIPCHECK(hipMemcpyAsync(dcol[1], h_time, 8 * r, hipMemcpyHostToDevice, st));
+  }
+  cc_events dev{};
+  TRY(hw_events(e, hev, &dev));
+  if (r == 0) {
+    if (hev) *hev->count = 0;
+    return CC_OK;
+  }
+  TRY(apply_staged(e, dcol, r, hout, hev, dev));
+  *h_applied = r;
+  return CC_OK;
+}
 
 extern "C" int cc_apply_batch_host(cc_engine* e, const cc_batch* h_cols, uint64_t n, const cc_results* h_out) {
   return apply_host(e, h_cols, n, h_out, nullptr);

@@ -4,8 +4,8 @@
 // InstanceQuery (@SerializeWith 30 / 31, manager/.../resource/InstanceCommand.java:26, InstanceQuery.java:26):
 // `writeLong(resource)` — the instance id — then `serializer.writeObject(operation)` (InstanceOperation.java:60-69).
 // The inner operation's @SerializeWith id is this engine's op code (include/copycat_apply.h), and its fields follow
-// its class's writeObject chain; kSchema below restates each one (file:line).  Manager operations
-// (GetResource 35, CreateResource 36, DeleteResource 37, ResourceExists 38: manager/.../manager/*.java) are decoded
+// its class's writeObject chain; kSchema (wire_plain.h, shared with the GPU decoder, wire_gpu.hip) restates each one
+// (file:line).  Manager operations (GetResource 35, CreateResource 36, DeleteResource 37, ResourceExists 38: manager/.../manager/*.java) are decoded
 // into control rows for cc_get_resource / cc_create_resource / cc_delete_resource / cc_resource_exists.
 //
 // Catalyst itself (Serializer, Buffer) is not vendored: its byte-level conventions — the identifier
@@ -18,105 +18,9 @@
 #include <vector>
 
 #include "engine_state.h"
+#include "wire_plain.h"
 
 namespace {
-
-// Catalyst Serializer identifier bytes: the width of the type id that follows (null has none)
-enum : uint8_t { kIdNull = 0x00, kIdInt8 = 0x01, kIdInt16 = 0x02, kIdInt24 = 0x03, kIdInt32 = 0x04, kIdClass = 0x05 };
-
-// operand slots of one op, in wire order
-enum Field : uint8_t {
-  F_END = 0,
-  F_KEY,      // serializer.writeObject(key): a non-null key -> key column + key tag
-  F_KEY_OPT,  // same, may be null (MultiMapCommands.Size() without a key): key 0
-  F_A,        // serializer.writeObject(value) -> operand a
-  F_B,        // serializer.writeObject(...) -> operand b
-  F_AUX,      // buffer.writeLong(ttl / timeout / delay) -> aux
-  F_LKEY,     // buffer.writeLong(member) -> key column, key tag LONG
-};
-
-struct Schema {
-  uint8_t op;
-  Field f[5];
-};
-
-// Field order per @SerializeWith id, from the writeObject chains of the reference's command classes.
-const Schema kSchema[] = {
-    // AtomicValueCommands.java: Get/Listen/Unlisten write nothing (:82,:249,:263); Set/GetAndSet write only the
-    // value (:126,:228 — they override ValueCommand.writeObject, so ttl never travels, A2); CompareAndSet
-    // expect, update (:182-184)
-    {CC_OP_VALUE_GET, {F_END}},
-    {CC_OP_VALUE_SET, {F_A, F_END}},
-    {CC_OP_VALUE_CAS, {F_A, F_B, F_END}},
-    {CC_OP_VALUE_GETANDSET, {F_A, F_END}},
-    {CC_OP_VALUE_LISTEN, {F_END}},
-    {CC_OP_VALUE_UNLISTEN, {F_END}},
-    // MapCommands.java: KeyQuery/KeyCommand key (:88,:119-121); ContainsValue value (:166-168); KeyValueCommand
-    // key, value (:200-202); TtlCommand key, value, ttl (:241-243); GetOrDefault key, default (:331-333);
-    // ReplaceIfPresent key, value, ttl, replace (:421-423); IsEmpty/Size/Clear nothing
-    {CC_OP_MAP_CONTAINSKEY, {F_KEY, F_END}},
-    {CC_OP_MAP_CONTAINSVALUE, {F_A, F_END}},
-    {CC_OP_MAP_PUT, {F_KEY, F_A, F_AUX, F_END}},
-    {CC_OP_MAP_PUTIFABSENT, {F_KEY, F_A, F_AUX, F_END}},
-    {CC_OP_MAP_GET, {F_KEY, F_END}},
-    {CC_OP_MAP_GETORDEFAULT, {F_KEY, F_A, F_END}},
-    {CC_OP_MAP_REMOVE, {F_KEY, F_END}},
-    {CC_OP_MAP_REMOVEIFPRESENT, {F_KEY, F_A, F_END}},
-    {CC_OP_MAP_REPLACE, {F_KEY, F_A, F_AUX, F_END}},
-    {CC_OP_MAP_REPLACEIFPRESENT, {F_KEY, F_A, F_AUX, F_B, F_END}},
-    {CC_OP_MAP_ISEMPTY, {F_END}},
-    {CC_OP_MAP_SIZE, {F_END}},
-    {CC_OP_MAP_CLEAR, {F_END}},
-    // MultiMapCommands.java: KeyQuery key (:121-123); EntryQuery key, value (:190-192); ValueQuery value
-    // (:154-156); TtlCommand key, value, ttl (:308-310); EntryCommand key, value (:267-269); RemoveValue value
-    // (:399-400); Size is a KeyQuery whose key may be null (:420-430)
-    {CC_OP_MMAP_CONTAINSKEY, {F_KEY, F_END}},
-    {CC_OP_MMAP_CONTAINSENTRY, {F_KEY, F_A, F_END}},
-    {CC_OP_MMAP_CONTAINSVALUE, {F_A, F_END}},
-    {CC_OP_MMAP_PUT, {F_KEY, F_A, F_AUX, F_END}},
-    {CC_OP_MMAP_GET, {F_KEY, F_END}},
-    {CC_OP_MMAP_REMOVE, {F_KEY, F_A, F_END}},
-    {CC_OP_MMAP_REMOVEVALUE, {F_A, F_END}},
-    {CC_OP_MMAP_ISEMPTY, {F_END}},
-    {CC_OP_MMAP_SIZE, {F_KEY_OPT, F_END}},
-    {CC_OP_MMAP_CLEAR, {F_END}},
-    // QueueCommands.java: ValueCommand / ValueQuery value (:87-88,:118-120); the rest nothing
-    {CC_OP_QUEUE_CONTAINS, {F_A, F_END}},
-    {CC_OP_QUEUE_ADD, {F_A, F_END}},
-    {CC_OP_QUEUE_OFFER, {F_A, F_END}},
-    {CC_OP_QUEUE_PEEK, {F_END}},
-    {CC_OP_QUEUE_POLL, {F_END}},
-    {CC_OP_QUEUE_ELEMENT, {F_END}},
-    {CC_OP_QUEUE_REMOVE, {F_A, F_END}},
-    {CC_OP_QUEUE_SIZE, {F_END}},
-    {CC_OP_QUEUE_ISEMPTY, {F_END}},
-    {CC_OP_QUEUE_CLEAR, {F_END}},
-    // SetCommands.java: the element travels as the key column (ValueCommand / ValueQuery value :87-88,:118-120);
-    // Add = TtlCommand element, ttl (:172-174)
-    {CC_OP_SET_CONTAINS, {F_KEY, F_END}},
-    {CC_OP_SET_ADD, {F_KEY, F_AUX, F_END}},
-    {CC_OP_SET_REMOVE, {F_KEY, F_END}},
-    {CC_OP_SET_SIZE, {F_END}},
-    {CC_OP_SET_ISEMPTY, {F_END}},
-    {CC_OP_SET_CLEAR, {F_END}},
-    // LeaderElectionCommands.java: nothing (:50,:69)
-    {CC_OP_ELECT_LISTEN, {F_END}},
-    {CC_OP_ELECT_UNLISTEN, {F_END}},
-    {CC_OP_ELECT_ISLEADER, {F_END}},
-    // LockCommands.java: Lock timeout (:80-81); Unlock nothing
-    {CC_OP_LOCK_LOCK, {F_AUX, F_END}},
-    {CC_OP_LOCK_UNLOCK, {F_END}},
-    // MembershipGroupCommands.java: Join/Leave nothing; Schedule member, delay, callback (:124-126); Execute
-    // member, callback (:172-174)
-    {CC_OP_GROUP_JOIN, {F_END}},
-    {CC_OP_GROUP_LEAVE, {F_END}},
-    {CC_OP_GROUP_SCHEDULE, {F_LKEY, F_AUX, F_A, F_END}},
-    {CC_OP_GROUP_EXECUTE, {F_LKEY, F_A, F_END}},
-    // TopicCommands.java: Listen / Unlisten nothing; Publish message (:100-108)
-    {CC_OP_TOPIC_LISTEN, {F_END}},
-    {CC_OP_TOPIC_UNLISTEN, {F_END}},
-    {CC_OP_TOPIC_PUBLISH, {F_A, F_END}},
-};
 
 const Schema* schema_of(uint32_t id) {
   static const std::vector<const Schema*> table = [] {  // (thread-safe one-time initialisation)
@@ -286,8 +190,10 @@ bool read_value(Reader& r, const cc_wire_codec& c, cc_wire_interner* in, uint32_
   return r.ok;
 }
 
+// One entry [p, end): reported as `row`, written to index `at` of `out` (cc_wire_decode: at = row; the GPU decoder's
+// fallback decodes its escaped rows into compact arrays).
 int decode_one(cc_engine* e, const cc_wire_codec& c, cc_wire_interner* in, const uint8_t* p, const uint8_t* end,
-               uint64_t row, const cc_wire_out* out) {
+               uint64_t row, uint64_t at, const cc_wire_out* out) {
   Reader r{p, end, c.big_endian != 0};
   const char* why = "truncated entry";
   auto fail = [&](const char* msg) { return set_err(CC_ERR_INVALID, (std::string("wire row ") + std::to_string(row) + ": " + msg).c_str()); };
@@ -302,30 +208,30 @@ int decode_one(cc_engine* e, const cc_wire_codec& c, cc_wire_interner* in, const
   };
   int64_t top = 0;
   if (!read_id(top)) return fail("entry is not a registered Catalyst type");
-  if (out->inst) out->inst[row] = e ? e->cfg.max_instances : 0;
-  if (out->iid) out->iid[row] = 0;
-  out->op[row] = 0;
-  out->flags[row] = 0;
-  out->key[row] = out->a[row] = out->b[row] = out->aux[row] = 0;
-  out->kind[row] = 0;
+  if (out->inst) out->inst[at] = e ? e->cfg.max_instances : 0;
+  if (out->iid) out->iid[at] = 0;
+  out->op[at] = 0;
+  out->flags[at] = 0;
+  out->key[at] = out->a[at] = out->b[at] = out->aux[at] = 0;
+  out->kind[at] = 0;
   if (top == 35 || top == 36 || top == 38) {  // GetResource / CreateResource / ResourceExists: key [, type]
     std::string key, type;
     bool null = false;
     if (!read_utf8(r, c, key, null)) return fail(why);
     if (null) return fail("resource key is null");
-    out->kind[row] = (uint8_t)top;
-    out->key[row] = intern(in, key);
+    out->kind[at] = (uint8_t)top;
+    out->key[at] = intern(in, key);
     if (top != 38) {  // buffer.writeInt(len).write(type name bytes) (GetResource.java:62-65, CreateResource.java:57-60)
       const uint64_t n = r.uint(4);
       const uint8_t* b = nullptr;
       if (!r.bytes(n, b)) return fail(why);
-      out->a[row] = res_type_of_class(std::string((const char*)b, n));
+      out->a[at] = res_type_of_class(std::string((const char*)b, n));
     }
     return r.p == end ? CC_OK : fail("trailing bytes after the manager operation");
   }
   if (top == 37) {  // DeleteResource: writeLong(resource) (DeleteResource.java:56)
-    out->kind[row] = 37;
-    out->b[row] = r.uint(8);
+    out->kind[at] = 37;
+    out->b[at] = r.uint(8);
     return r.ok && r.p == end ? CC_OK : fail(why);
   }
   if (top != 30 && top != 31) return fail("not an InstanceCommand / InstanceQuery / manager operation");
@@ -334,12 +240,12 @@ int decode_one(cc_engine* e, const cc_wire_codec& c, cc_wire_interner* in, const
   if (!read_id(id)) return fail("inner operation is not a registered Catalyst type");
   const Schema* s = (id >= 0 && id < 256) ? schema_of((uint32_t)id) : nullptr;
   if (!s) return fail("inner operation id is no resource operation this engine knows");
-  if (out->iid) out->iid[row] = iid;
+  if (out->iid) out->iid[at] = iid;
   if (e) {
     auto it = e->inst_by_id.find(iid);
-    out->inst[row] = it == e->inst_by_id.end() ? e->cfg.max_instances : it->second;  // unknown: UNKNOWN_SESSION
+    out->inst[at] = it == e->inst_by_id.end() ? e->cfg.max_instances : it->second;  // unknown: UNKNOWN_SESSION
   }
-  out->op[row] = s->op;
+  out->op[at] = s->op;
   uint32_t ta = CC_TAG_NULL, tb = CC_TAG_NULL, kt = 0;
   for (int k = 0; k < 5 && s->f[k] != F_END; ++k) {
     uint32_t tag = 0;
@@ -353,21 +259,21 @@ int decode_one(cc_engine* e, const cc_wire_codec& c, cc_wire_interner* in, const
           break;
         }
         kt = tag == CC_TAG_LONG ? 0u : tag == CC_TAG_INT ? 1u : tag == CC_TAG_BOOL ? 2u : 3u;
-        out->key[row] = v;
+        out->key[at] = v;
         break;
       case F_A:
         if (!read_value(r, c, in, ta, v, &why)) return fail(why);
-        out->a[row] = v;
+        out->a[at] = v;
         break;
       case F_B:
         if (!read_value(r, c, in, tb, v, &why)) return fail(why);
-        out->b[row] = v;
+        out->b[at] = v;
         break;
       case F_AUX:
-        out->aux[row] = r.uint(8);
+        out->aux[at] = r.uint(8);
         break;
       case F_LKEY:
-        out->key[row] = r.uint(8);
+        out->key[at] = r.uint(8);
         kt = 0;
         break;
       case F_END:
@@ -376,11 +282,28 @@ int decode_one(cc_engine* e, const cc_wire_codec& c, cc_wire_interner* in, const
     if (!r.ok) return fail("truncated entry");
   }
   if (r.p != end) return fail("trailing bytes after the operation's fields");
-  out->flags[row] = CC_FLAGS(ta, tb, kt);
+  out->flags[at] = CC_FLAGS(ta, tb, kt);
   return CC_OK;
 }
 
 }  // namespace
+
+// what wire_gpu.hip's fallback needs of this unit (engine_internal.h)
+int cc::wire_decode_one(cc_engine* e, const cc_wire_codec& c, cc_wire_interner* in, const uint8_t* p, const uint8_t* end,
+                        uint64_t row, uint64_t at, const cc_wire_out* out) {
+  return decode_one(e, c, in, p, end, row, at, out);
+}
+
+int cc::wire_register_keys(cc_engine* e, cc_wire_interner* in, const uint64_t* keys, uint64_t m) {
+  std::vector<uint64_t> hk;
+  std::vector<int32_t> hv;
+  for (uint64_t i = 0; i < m; ++i)
+    if (keys[i] >= in->first && keys[i] - in->first < in->hashes.size() && !e->hh.count(keys[i])) {
+      hk.push_back(keys[i]);
+      hv.push_back(in->hashes[keys[i] - in->first]);
+    }
+  return hk.empty() ? CC_OK : cc_handle_hashes(e, hk.data(), hv.data(), hk.size());
+}
 
 extern "C" void cc_wire_codec_default(cc_wire_codec* c) {
   if (!c) return;
@@ -446,7 +369,7 @@ extern "C" int cc_wire_decode(cc_engine* e, const cc_wire_codec* codec, cc_wire_
       if (bad_row) *bad_row = i;
       return set_err(CC_ERR_INVALID, "wire decode: entry ends past the buffer");
     }
-    const int rc = decode_one(e, c, in, buf + offsets[i], buf + offsets[i + 1], i, out);
+    const int rc = decode_one(e, c, in, buf + offsets[i], buf + offsets[i + 1], i, i, out);
     if (rc) {
       if (bad_row) *bad_row = i;
       return rc;

@@ -1,0 +1,388 @@
+// wire_gpu.hip — the Catalyst wire format decoded on the GPU: wire bytes in, the ordinary wide columns in HBM out
+// (include/copycat_apply.h "the same decode on the GPU"; the format and the host decoder: wire.cpp, wire_plain.h).
+//
+// k_wire_decode: one workgroup of 256 lanes per tile of CC_WIRE_TILE_ROWS consecutive entries, taken as groups of 256
+// entries, lane i the i-th entry of the group.
+//   1. Staging.  An entry longer than the longest plain entry (kWirePlainMax, 65 bytes) escapes without a byte being
+//      read.  The others' bytes go global -> LDS with 16-byte loads, lane i the i-th 16 bytes, through a fixed window
+//      of kWin bytes that starts at the (16-byte-aligned) start of the first entry still to parse: kWin holds any 256
+//      consecutive short entries, so a group of short entries is one window; a long String entry in the group ends a
+//      window early, and the entries the window's end cuts are parsed from the next window, which starts at the first
+//      of them.  Each window parses at least its first entry, so the loop ends.
+//   2. Parse.  One lane parses one entry from LDS with the parser the host decoder is checked against
+//      (wire_plain_parse).  Single bytes are byte reads; the 8-byte and 4-byte fields, unaligned and big-endian, are
+//      three (two) aligned dword reads joined by v_alignbyte_b32 and one byte swap, not eight byte reads.
+//   3. Instance lookup.  inst = the slot of the instance id in the engine's device hash table (open addressing,
+//      linear probing, at most half full); an unknown id gives max_instances.
+//   4. Output.  The group's rows go to LDS and leave as 16-byte stores, lane j the j-th 16 bytes of a column: two u64
+//      rows, four u32 rows or sixteen u8 rows per lane (narrow stores cost several times a 16-byte store per byte:
+//      unpack.hip).  The last partial 16 bytes of a column's tail are stored row by row.
+//   5. Escapes.  A row that is not plain gets the host decoder's defaults (inst = max_instances, everything else 0)
+//      and one bit in the escape bitmap: each wave stores the ballot of its 64 rows as one word, so the rows come out
+//      in row order by construction; the count is one atomic add per wave that has any.
+// The host (wire_to_device) decodes the escaped rows with wire.cpp's decode_one, in ascending row order, and
+// k_wire_patch writes them over the columns.
+// The kernel moves (entry bytes + 8 B offset + 38 B columns) per row once; its bar is the H2D of its own input.
+// Measured (scripts/wire_rate.py, profiles/wire_gpu/rate.json: 16 Mi CompareAndSet entries of 34 bytes, MI355X): the
+// kernel takes 0.77 ms (1.7 TB/s over those bytes), the H2D of the same input 12.5 ms.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): k_wire_decode 95 VGPRs, 106 SGPRs (252 SGPR spills,
+// to VGPR lanes), no scratch, 29,504 B LDS, occupancy 5 waves / SIMD; k_wire_patch 30 VGPRs, no scratch, no LDS.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "engine_state.h"
+#include "wire_plain.h"
+
+namespace cc {
+
+namespace {
+
+constexpr uint32_t kWireLanes = 256;
+constexpr uint32_t kWaves = kWireLanes / 64;
+constexpr uint32_t kWireTile = CC_WIRE_TILE_ROWS;
+static_assert(kWireTile % kWireLanes == 0, "a tile is whole groups of 256 entries");
+// the window: 256 short entries behind a start up to 15 bytes past a 16-byte boundary, in whole 16-byte loads; the
+// LDS array has 16 bytes more, for the aligned dwords an 8-byte field's read may touch past the window
+constexpr uint32_t kWin = (15 + kWireLanes * kWirePlainMax + 15) / 16 * 16;
+
+// an entry in the LDS window, starting at byte `base` of it
+struct LdsBytes {
+  const uint8_t* win;
+  uint32_t base;
+  __device__ uint32_t u8(uint32_t i) const { return win[base + i]; }
+  __device__ uint32_t le32(uint32_t i) const {
+    const uint32_t at = base + i;
+    const uint32_t* w = (const uint32_t*)(win + (at & ~3u));
+    return __builtin_amdgcn_alignbyte(w[1], w[0], at & 3u);
+  }
+  __device__ uint64_t le64(uint32_t i) const {
+    const uint32_t at = base + i;
+    const uint32_t* w = (const uint32_t*)(win + (at & ~3u));
+    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+    return (uint64_t)__builtin_amdgcn_alignbyte(w1, w0, at & 3u) |
+           ((uint64_t)__builtin_amdgcn_alignbyte(w2, w1, at & 3u) << 32);
+  }
+};
+
+__device__ inline uint32_t slot_of(const WireArgs& a, uint64_t id) {
+  uint32_t h = (uint32_t)((id * 0x9E3779B97F4A7C15ull) >> 32) & a.tbl_mask;
+  for (uint32_t probe = 0; probe <= a.tbl_mask; ++probe) {  // (the table is at most half full: an empty cell ends it)
+    const uint32_t s = a.tbl_slot[h];
+    if (s == ~0u) break;
+    if (a.tbl_id[h] == id) return s;
+    h = (h + 1) & a.tbl_mask;
+  }
+  return a.max_inst;
+}
+
+// rows [0, rows) of one column of the group: LDS -> global, 16 bytes per lane
+template <class T>
+__device__ inline void store_col(T* out, const T* lds, uint32_t rows) {
+  constexpr uint32_t per = 16 / sizeof(T);
+  for (uint32_t c = threadIdx.x; c * per < rows; c += kWireLanes) {
+    if ((c + 1) * per <= rows) {
+      *(uint4*)(out + c * per) = *(const uint4*)(lds + c * per);
+    } else {
+      for (uint32_t j = c * per; j < rows; ++j) out[j] = lds[j];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_wire_decode(WireArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t win[kWin + 16];
+  __shared__ __attribute__((aligned(16))) uint64_t o64[5][kWireLanes];  // key, a, b, aux, iid
+  __shared__ __attribute__((aligned(16))) uint32_t o32[kWireLanes];     // inst
+  __shared__ __attribute__((aligned(16))) uint8_t o8[2][kWireLanes];    // op, flags
+  __shared__ uint32_t s_sch[kSchemaIds];
+  __shared__ uint64_t s_first[kWaves];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  s_sch[tid] = a.schema[tid];
+  static_assert(kSchemaIds == kWireLanes, "one schema word per lane");
+  const uint64_t t0 = (uint64_t)blockIdx.x * kWireTile;
+  const uint64_t base0 = a.off[0];
+  for (uint32_t g = 0; g < kWireTile / kWireLanes; ++g) {
+    const uint64_t g0 = t0 + (uint64_t)g * kWireLanes;
+    if (g0 >= a.n) break;  // (the same in every lane)
+    const uint32_t rows = (uint32_t)min((uint64_t)kWireLanes, a.n - g0);
+    const bool valid = tid < rows;
+    const uint64_t beg = valid ? a.off[g0 + tid] - base0 : 0, end = valid ? a.off[g0 + tid + 1] - base0 : 0;
+    const uint64_t gend = a.off[g0 + rows] - base0;
+    bool pend = valid && end - beg <= kWirePlainMax;  // still to parse; the longer ones escape unread
+    bool plain = false;
+    PlainRow r{};
+    for (;;) {
+      const uint64_t bal = __ballot(pend);
+      const uint64_t first = __shfl((unsigned long long)beg, bal ? __ffsll((unsigned long long)bal) - 1 : 0);
+      if (lane == 0) s_first[wave] = bal ? first : ~0ull;
+      __syncthreads();  // (every lane is also done with the previous window)
+      const uint64_t wb = min(min(s_first[0], s_first[1]), min(s_first[2], s_first[3]));
+      if (wb == ~0ull) break;  // nothing left to parse in the group (the same in every lane)
+      const uint64_t wbase = wb & ~15ull;
+      const uint32_t lim = (uint32_t)min((uint64_t)kWin, ((gend + 15) & ~15ull) - wbase);
+      for (uint32_t i = tid * 16; i < lim; i += kWireLanes * 16) *(uint4*)(win + i) = *(const uint4*)(a.bytes + wbase + i);
+      __syncthreads();
+      if (pend && end <= wbase + kWin) {
+        pend = false;
+        plain = wire_plain_parse(LdsBytes{win, (uint32_t)(beg - wbase)}, (uint32_t)(end - beg), a.codec, s_sch, r);
+      }
+    }
+    o64[0][tid] = plain ? r.key : 0;
+    o64[1][tid] = plain ? r.a : 0;
+    o64[2][tid] = plain ? r.b : 0;
+    o64[3][tid] = plain ? r.aux : 0;
+    o64[4][tid] = plain ? r.iid : 0;
+    o32[tid] = plain ? slot_of(a, r.iid) : a.max_inst;
+    o8[0][tid] = plain ? r.op : 0;
+    o8[1][tid] = plain ? r.flags : 0;
+    const uint64_t esc = __ballot(valid && !plain);
+    if (lane == 0 && g0 + wave * 64 < a.n) {
+      a.esc[(g0 >> 6) + wave] = esc;
+      if (esc) atomicAdd(a.esc_n, (unsigned long long)__popcll(esc));
+    }
+    __syncthreads();
+    store_col(a.key + g0, o64[0], rows);
+    store_col(a.a + g0, o64[1], rows);
+    store_col(a.b + g0, o64[2], rows);
+    store_col(a.aux + g0, o64[3], rows);
+    if (a.iid) store_col(a.iid + g0, o64[4], rows);
+    store_col(a.inst + g0, o32, rows);
+    store_col(a.op + g0, o8[0], rows);
+    store_col(a.flags + g0, o8[1], rows);
+    __syncthreads();  // (the next group writes the LDS columns again)
+  }
+}
+
+// host-decoded rows over the columns: one lane per row (sparse rows: narrow stores)
+__global__ __launch_bounds__(256) void k_wire_patch(WireArgs a, const WirePatch* rows, uint64_t m) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= m) return;
+  const WirePatch p = rows[i];
+  if (p.row >= a.n) return;
+  a.inst[p.row] = p.inst;
+  a.op[p.row] = p.op;
+  a.flags[p.row] = p.flags;
+  a.key[p.row] = p.key;
+  a.a[p.row] = p.a;
+  a.b[p.row] = p.b;
+  a.aux[p.row] = p.aux;
+  if (a.iid) a.iid[p.row] = p.iid;
+}
+
+enum WrSlot : int { kWrBytes = 0, kWrOff, kWrEsc, kWrTable, kWrSchema, kWrPatch };
+
+// device buffer `slot` of the decoder with room for `bytes` (contents not kept; the calls are synchronous)
+int wr(cc_engine* e, int slot, size_t bytes, void** out) {
+  bytes = std::max<size_t>(bytes, 256);
+  if (e->wr_cap[slot] < bytes) {
+    const size_t cap = std::max(bytes, e->wr_cap[slot] * 3 / 2);
+    if (e->wr_buf[slot]) (void)hipFree(e->wr_buf[slot]);
+    e->wr_buf[slot] = nullptr;
+    e->wr_cap[slot] = 0;
+    const hipError_t x = hipMalloc(&e->wr_buf[slot], cap);
+    if (x != hipSuccess) return set_err(CC_ERR_HIP, "hipMalloc (wire decoder staging)", x);
+    e->wr_cap[slot] = cap;
+  }
+  *out = e->wr_buf[slot];
+  return CC_OK;
+}
+
+// The device table instance id -> slot, rebuilt from the session registry when it has changed: the host builds the
+// image (ids, then slots) and one H2D sends it.
+int wire_table(cc_engine* e, hipStream_t st) {
+  if (e->wr_gen == e->inst_gen && e->wr_buf[kWrTable]) return CC_OK;
+  uint64_t cells = 64;
+  while (cells < 2ull * e->cfg.max_instances) cells <<= 1;
+  if (cells > (1ull << 31)) return set_err(CC_ERR_CAPACITY, "wire decode: instance table");
+  const uint32_t mask = (uint32_t)(cells - 1);
+  std::vector<uint64_t> img(cells + (cells + 1) / 2, 0);
+  uint32_t* slots = (uint32_t*)(img.data() + cells);
+  for (uint64_t i = 0; i < cells; ++i) slots[i] = ~0u;
+  for (const auto& kv : e->inst_by_id) {
+    uint32_t h = wire_tbl_hash(kv.first, mask);
+    while (slots[h] != ~0u) h = (h + 1) & mask;
+    img[h] = kv.first;
+    slots[h] = kv.second;
+  }
+  void* d = nullptr;
+  TRY(wr(e, kWrTable, img.size() * 8, &d));
+  HIPCHECK(hipMemcpyAsync(d, img.data(), img.size() * 8, hipMemcpyHostToDevice, st));
+  HIPCHECK(hipStreamSynchronize(st));  // (img leaves scope)
+  e->wr_mask = mask;
+  e->wr_gen = e->inst_gen;
+  return CC_OK;
+}
+
+}  // namespace
+
+int launch_wire_decode(const WireArgs& a, hipStream_t st) {
+  if (a.n == 0) return 0;
+  const uint64_t tiles = (a.n + kWireTile - 1) / kWireTile;
+  if (tiles > 0x7FFFFFFFull) return -1;
+  hipLaunchKernelGGL(k_wire_decode, dim3((uint32_t)tiles), dim3(kWireLanes), 0, st, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_wire_patch(const WireArgs& a, const WirePatch* rows, uint64_t m, hipStream_t st) {
+  if (m == 0) return 0;
+  hipLaunchKernelGGL(k_wire_patch, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, st, a, rows, m);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int wire_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* in, const uint8_t* h_buf, uint64_t buf_len,
+                   const uint64_t* h_offsets, uint64_t n, const cc_batch_out* d_cols, uint64_t* d_iid,
+                   cc_wire_control* h_ctl, uint64_t ctl_cap, uint64_t* ctl_count, cc_wire_stats* stats, hipStream_t st,
+                   uint64_t* bad_row, bool stop_at_ctl, uint64_t* stop_row) {
+  if (!e || !in || !h_buf || !h_offsets || !d_cols || !ctl_count || (ctl_cap && !h_ctl))
+    return set_err(CC_ERR_INVALID, "wire decode: null argument");
+  void* const col[7] = {d_cols->inst, d_cols->op, d_cols->flags, d_cols->key, d_cols->a, d_cols->b, d_cols->aux};
+  for (void* p : col)
+    if (!p || ((uintptr_t)p & 15))
+      return set_err(CC_ERR_INVALID, "wire decode: a device column is null or not 16-byte aligned");
+  if ((uintptr_t)d_iid & 15) return set_err(CC_ERR_INVALID, "wire decode: d_iid is not 16-byte aligned");
+  cc_wire_codec c;
+  if (codec) c = *codec;
+  else cc_wire_codec_default(&c);
+  if (c.utf8_len_bytes < 1 || c.utf8_len_bytes > 8) return set_err(CC_ERR_INVALID, "wire codec: utf8_len_bytes");
+  *ctl_count = 0;
+  if (stop_row) *stop_row = n;
+  if (stats) *stats = cc_wire_stats{n, 0, 0};
+  if (n == 0) return CC_OK;
+  HIPCHECK(hipSetDevice(e->device));
+  // the rows before the first offsets violation go to the device (its row fails the call, unless a row before it does)
+  uint64_t m = n;
+  for (uint64_t i = 0; i < n; ++i)
+    if (h_offsets[i + 1] < h_offsets[i] || h_offsets[i + 1] > buf_len) {
+      m = i;
+      break;
+    }
+  WireArgs a{};
+  a.n = m;
+  a.codec = c;
+  a.max_inst = e->cfg.max_instances;
+  a.inst = (uint32_t*)col[0], a.op = (uint8_t*)col[1], a.flags = (uint8_t*)col[2];
+  a.key = (uint64_t*)col[3], a.a = (uint64_t*)col[4], a.b = (uint64_t*)col[5], a.aux = (uint64_t*)col[6];
+  a.iid = d_iid;
+  std::vector<uint64_t> esc;  // the escape bitmap
+  uint64_t esc_n = 0;
+  if (m) {
+    // staging: bytes [offsets[0], offsets[m]) at the start of a buffer padded to whole 16-byte loads, the offsets as
+    // they are (the kernel subtracts offsets[0])
+    const uint64_t span = h_offsets[m] - h_offsets[0];
+    void *d_bytes, *d_off, *d_esc, *d_sch;
+    TRY(wr(e, kWrBytes, ((span + 15) & ~15ull) + 16, &d_bytes));
+    TRY(wr(e, kWrOff, 8 * (m + 1), &d_off));
+    const uint64_t words = (m + 63) / 64;
+    TRY(wr(e, kWrEsc, 16 + 8 * words, &d_esc));  // the count, then (16-byte aligned) the bitmap
+    if (!e->wr_buf[kWrSchema]) {
+      uint32_t sch[kSchemaIds];
+      schema_words(sch);
+      TRY(wr(e, kWrSchema, sizeof sch, &d_sch));
+      HIPCHECK(hipMemcpy(d_sch, sch, sizeof sch, hipMemcpyHostToDevice));
+    }
+    d_sch = e->wr_buf[kWrSchema];
+    if (!e->wr_pin) HIPCHECK(hipHostMalloc((void**)&e->wr_pin, 64, hipHostMallocDefault));
+    TRY(wire_table(e, st));
+    for (hipEvent_t& ev : e->wr_ev)
+      if (!ev) HIPCHECK(hipEventCreate(&ev));
+    HIPCHECK(hipEventRecord(e->wr_ev[0], st));
+    if (span) HIPCHECK(hipMemcpyAsync(d_bytes, h_buf + h_offsets[0], span, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_off, h_offsets, 8 * (m + 1), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemsetAsync(d_esc, 0, 16, st));
+    a.bytes = (const uint8_t*)d_bytes;
+    a.off = (const uint64_t*)d_off;
+    a.schema = (const uint32_t*)d_sch;
+    a.tbl_id = (const uint64_t*)e->wr_buf[kWrTable];
+    a.tbl_slot = (const uint32_t*)(a.tbl_id + (e->wr_mask + 1ull));
+    a.tbl_mask = e->wr_mask;
+    a.esc_n = (unsigned long long*)d_esc;
+    a.esc = (uint64_t*)d_esc + 2;
+    HIPCHECK(hipEventRecord(e->wr_ev[1], st));
+    if (launch_wire_decode(a, st)) return set_err(CC_ERR_HIP, "wire decode launch", hipGetLastError());
+    HIPCHECK(hipEventRecord(e->wr_ev[2], st));
+    HIPCHECK(hipMemcpyAsync(e->wr_pin, d_esc, 8, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    esc_n = e->wr_pin[0];
+    if (esc_n) {
+      esc.resize(words);
+      HIPCHECK(hipMemcpyAsync(esc.data(), a.esc, 8 * words, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHECK(hipEventRecord(e->wr_ev[3], st));
+    HIPCHECK(hipStreamSynchronize(st));
+    e->wr_timed = true;
+  }
+  // the fallback: every escaped row through the host decoder, in ascending row order
+  std::vector<WirePatch> patch;
+  std::vector<cc_wire_control> ctl;
+  std::vector<uint64_t> skeys;  // String keys, registered on success
+  uint64_t fail_row = ~0ull, stop = n;
+  int fail_rc = CC_OK;
+  bool stopped = false;
+  patch.reserve(esc_n);
+  for (uint64_t w = 0; w < esc.size() && fail_rc == CC_OK && !stopped; ++w)
+    for (uint64_t bits = esc[w]; bits; bits &= bits - 1) {
+      const uint64_t row = w * 64 + (uint64_t)__builtin_ctzll(bits);
+      WirePatch p{};
+      uint8_t kind = 0;
+      const cc_wire_out o{&p.inst, &p.iid, &p.op, &p.flags, &p.key, &p.a, &p.b, &p.aux, &kind};
+      const int rc = wire_decode_one(e, c, in, h_buf + h_offsets[row], h_buf + h_offsets[row + 1], row, 0, &o);
+      if (rc) {
+        fail_rc = rc, fail_row = row;
+        break;
+      }
+      p.row = row;
+      patch.push_back(p);
+      if (kind) {
+        ctl.push_back(cc_wire_control{row, kind, p.key, p.a, p.b});
+        if (stop_at_ctl) {
+          stopped = true, stop = row;
+          break;
+        }
+      } else if (CC_FLAG_KTAG(p.flags) == 3u) {
+        skeys.push_back(p.key);
+      }
+    }
+  if (!patch.empty()) {
+    void* d_patch;
+    TRY(wr(e, kWrPatch, patch.size() * sizeof(WirePatch), &d_patch));
+    HIPCHECK(hipMemcpyAsync(d_patch, patch.data(), patch.size() * sizeof(WirePatch), hipMemcpyHostToDevice, st));
+    if (launch_wire_patch(a, (const WirePatch*)d_patch, patch.size(), st))
+      return set_err(CC_ERR_HIP, "wire patch launch", hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+  }
+  if (stats) stats->host_rows = patch.size(), stats->device_rows = m - std::min<uint64_t>(m, esc_n);
+  if (fail_rc) {  // (cc_last_error holds decode_one's "wire row N: ...")
+    if (bad_row) *bad_row = fail_row;
+    return fail_rc;
+  }
+  if (!stopped && m < n) {
+    if (bad_row) *bad_row = m;
+    return set_err(CC_ERR_INVALID, h_offsets[m + 1] < h_offsets[m] ? "wire decode: offsets decrease"
+                                                                   : "wire decode: entry ends past the buffer");
+  }
+  if (stop_row) *stop_row = stop;
+  TRY(wire_register_keys(e, in, skeys.data(), skeys.size()));
+  *ctl_count = ctl.size();
+  if (ctl.size() > ctl_cap) return set_err(CC_ERR_CAPACITY, "wire decode: more manager entries than h_ctl holds");
+  if (!ctl.empty()) memcpy(h_ctl, ctl.data(), ctl.size() * sizeof(cc_wire_control));
+  return CC_OK;
+}
+
+}  // namespace cc
+
+extern "C" int cc_wire_timeline(cc_engine* e, float* h_ms) {
+  if (!e || !h_ms) return set_err(CC_ERR_INVALID, "null argument");
+  if (!e->wr_timed) return set_err(CC_ERR_STATE, "wire timeline: no decode has run on this engine");
+  for (int k = 0; k < 3; ++k) HIPCHECK(hipEventElapsedTime(&h_ms[k], e->wr_ev[k], e->wr_ev[k + 1]));
+  return CC_OK;
+}
+
+extern "C" int cc_wire_decode_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* in, const uint8_t* h_buf,
+                                        uint64_t buf_len, const uint64_t* h_offsets, uint64_t n,
+                                        const cc_batch_out* d_cols, uint64_t* d_iid, cc_wire_control* h_ctl,
+                                        uint64_t ctl_cap, uint64_t* ctl_count, cc_wire_stats* stats, void* stream,
+                                        uint64_t* bad_row) {
+  return wire_to_device(e, codec, in, h_buf, buf_len, h_offsets, n, d_cols, d_iid, h_ctl, ctl_cap, ctl_count, stats,
+                        (hipStream_t)stream, bad_row, false, nullptr);
+}

@@ -107,6 +107,9 @@ def lib():
             "cc_wire_string_hash": (i32, [P, u64, P]),
             "cc_handle_hashes": (i32, [P, P, P, u64]),
             "cc_wire_decode": (i32, [P, P, P, P, u64, P, u64, P, P]),
+            "cc_wire_decode_to_device": (i32, [P, P, P, P, u64, P, u64, P, P, P, u64, P, P, P, P]),
+            "cc_wire_timeline": (i32, [P, P]),
+            "cc_apply_wire_host": (i32, [P, P, P, P, u64, P, u64, P, P, P, P, P, P]),
             "cc_split_batch": (i32, [P, u64, P, u32, u32, u32, P, P, P, P]),
             "cc_apply_batch_host_prefix": (i32, [P, P, u64, P, P, P]),
             "cc_apply_batch_prefix": (i32, [P, P, u64, P, P, P, P]),
@@ -360,6 +363,42 @@ class Engine:
         self.apply_events(db, status, value, evs)
         self.sync()
         return status.cpu().numpy(), value.cpu().numpy().view(np.uint64), evs.host()
+
+    def apply_wire_host(self, decoder, index, time=None, entries=None, buf=None, offsets=None, capacity=None):
+        """cc_apply_wire_host: the log segment itself (entries, or buf + offsets; `decoder` a WireDecoder on this engine)
+        decoded on the GPU and applied up to the first manager entry -> (status, value, events, applied, control);
+        control is None or the manager entry at row `applied` as a dict (row, kind, key, a, b): the host runs it and
+        calls again from row applied + 1."""
+        buf, offsets = decoder._segment(entries, buf, offsets)
+        n = len(offsets) - 1
+        index = np.ascontiguousarray(index, np.uint64)
+        time = None if time is None else np.ascontiguousarray(time, np.uint64)
+        assert len(index) == n and (time is None or len(time) == n)
+        status = np.full(n, RESULT_SENTINEL, np.uint8)
+        value = np.zeros(n, np.uint64)
+        cap = capacity if capacity is not None else max(4 * n, 1024)
+        ev = {"pos": np.zeros(cap, np.uint32), "target": np.zeros(cap, np.uint32), "code": np.zeros(cap, np.uint8),
+              "src": np.zeros(cap, np.uint8), "tag": np.zeros(cap, np.uint8), "payload": np.zeros(cap, np.uint64)}
+        count = C.c_uint64(0)
+        hev = abi.cc_events(*(ev[k].ctypes.data for k in ("pos", "target", "code", "src", "tag", "payload")), cap,
+                            C.cast(C.byref(count), C.c_void_p))
+        r = abi.cc_results(status.ctypes.data, value.ctypes.data)
+        applied = C.c_uint64(0)
+        ctl = abi.cc_wire_control()
+        _check(self.L.cc_apply_wire_host(self.h, C.byref(decoder.codec), decoder.interner.h, _np(buf), buf.size,
+                                         _np(offsets), n, _np(index), _np(time) if time is not None else None,
+                                         C.byref(r), C.byref(hev), C.byref(applied), C.byref(ctl)))
+        m = applied.value
+        control = None
+        if m < n:
+            control = {k: int(getattr(ctl, k)) for k in ("row", "kind", "key", "a", "b")}
+        return status[:m], value[:m], {k: v[:count.value] for k, v in ev.items()}, m, control
+
+    def wire_timeline(self):
+        """cc_wire_timeline: (H2D, kernel, escape round trip) milliseconds of the last decode on the device."""
+        ms = (C.c_float * 3)()
+        _check(self.L.cc_wire_timeline(self.h, ms))
+        return tuple(float(x) for x in ms)
 
     def apply_host(self, b: Batch):
         """PCIe-inclusive path: host columns in, host results out (H2D + apply + D2H + sync)."""

@@ -57,11 +57,58 @@ class WireDecoder:
         self.interner = interner or Interner()
         self.codec = codec or default_codec()
 
-    def decode(self, entries=None, buf=None, offsets=None):
+    @staticmethod
+    def _segment(entries, buf, offsets, check=True):
         if entries is not None:
             offsets = np.zeros(len(entries) + 1, np.uint64)
             offsets[1:] = np.cumsum([len(e) for e in entries])
             buf = np.frombuffer(b"".join(entries) or b"\0", np.uint8)
+        buf = np.ascontiguousarray(buf, np.uint8)  # (a contiguous uint8 view, an odd address included, stays as it is)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        if check and len(offsets) > 1 and int(offsets[-1]) > buf.size:
+            raise ValueError(f"offsets end at {int(offsets[-1])} past the {buf.size}-byte buffer")
+        return buf, offsets
+
+    def decode_to_device(self, entries=None, buf=None, offsets=None, device="cuda", stream=None, ctl_cap=None,
+                         check_offsets=True):
+        """cc_wire_decode_to_device: the same decode with the plain entries parsed on the GPU and the columns left in
+        device memory -> (DeviceBatch, iid tensor, kind, stats).  kind (numpy, as decode's) is rebuilt from the control
+        list; stats is a dict (rows, device_rows, host_rows).  The DeviceBatch's index / time columns are zero: they
+        are the log entries' own."""
+        import torch
+
+        from .engine import DeviceBatch, _stream_ptr
+
+        assert self.engine is not None, "decode_to_device needs an engine"
+        buf, offsets = self._segment(entries, buf, offsets, check_offsets)
+        n = len(offsets) - 1
+        cols = {}
+        for name, dt in abi.BATCH_COLUMNS:
+            cols[name] = torch.zeros(max(n, 1), dtype={"u8": torch.int64, "u4": torch.int32, "u1": torch.uint8}[dt],
+                                     device=device).view(DeviceBatch.TORCH_DT[dt])[:n]
+        iid = torch.zeros(max(n, 1), dtype=torch.int64, device=device).view(torch.uint64)[:n]
+        out = abi.cc_batch_out()
+        for name in ("inst", "op", "flags", "key", "a", "b", "aux"):
+            setattr(out, name, cols[name].data_ptr())
+        cap = n if ctl_cap is None else ctl_cap
+        ctl = (abi.cc_wire_control * max(cap, 1))()
+        nctl = C.c_uint64(0)
+        stats = abi.cc_wire_stats()
+        bad = C.c_uint64(~0 & 0xFFFFFFFFFFFFFFFF)
+        torch.cuda.synchronize()  # (the zero fills above run on torch's stream)
+        rc = lib().cc_wire_decode_to_device(self.engine.h, C.byref(self.codec), self.interner.h, _np(buf), buf.size,
+                                            _np(offsets), n, C.byref(out), iid.data_ptr(), ctl, cap, C.byref(nctl),
+                                            C.byref(stats), _stream_ptr(stream), C.byref(bad))
+        self.bad_row, self.ctl_count = bad.value, nctl.value
+        self.last_device = (DeviceBatch(cols, n), iid)  # (what a failed call decoded, for inspection)
+        _check(rc)
+        kind = np.zeros(n, np.uint8)
+        for k in range(nctl.value):
+            kind[ctl[k].row] = ctl[k].kind
+        return DeviceBatch(cols, n), iid, kind, {k: int(getattr(stats, k)) for k in ("rows", "device_rows", "host_rows")}
+
+    def decode(self, entries=None, buf=None, offsets=None):
+        buf, offsets = self._segment(entries, buf, offsets)
         n = len(offsets) - 1
         b = Batch(n)
         iid = np.zeros(n, np.uint64)
@@ -70,10 +117,6 @@ class WireDecoder:
                               a=_np(b.a), b=_np(b.b), aux=_np(b.aux), kind=_np(kind))
         bad = C.c_uint64(~0 & 0xFFFFFFFFFFFFFFFF)
         eh = self.engine.h if self.engine is not None else None
-        buf = np.ascontiguousarray(buf, np.uint8)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        if n and int(offsets[-1]) > buf.size:
-            raise ValueError(f"offsets end at {int(offsets[-1])} past the {buf.size}-byte buffer")
         _check(lib().cc_wire_decode(eh, C.byref(self.codec), self.interner.h, _np(buf), buf.size, _np(offsets), n,
                                     C.byref(out), C.byref(bad)))
         return b, iid, kind

@@ -637,6 +637,63 @@ int  cc_split_batch(const cc_batch* in, uint64_t n, const uint8_t* rank_of_inst,
 int  cc_merge_results(const uint32_t* inst, uint64_t n, const uint8_t* rank_of_inst, uint32_t n_inst, uint32_t world,
                       uint32_t threads, const cc_results* parts, const cc_results* out);
 
+/* ---- the same decode on the GPU: wire bytes in, device columns out (copycat_amd/csrc/wire_plain.h, wire_gpu.hip) ----
+ * These calls exist from this commit on, under the unchanged CC_ABI_VERSION 6 (symbols are only added).
+ * A Copycat host holds the log's serialized entries, not columns.  cc_wire_decode_to_device takes the log segment
+ * itself (host bytes + offsets) and leaves the decoded columns in device memory, byte for byte what cc_wire_decode
+ * gives for the same input.  A gfx950 kernel (k_wire_decode; a workgroup per CC_WIRE_TILE_ROWS consecutive entries,
+ * one lane per entry) decodes the PLAIN entries: InstanceCommand / InstanceQuery whose inner id is a known operation
+ * and whose writeObject fields are all null / Long / Integer / Boolean under the codec.  Everything else ESCAPES to
+ * the host decoder, in ascending row order, and its row is written over the device columns afterwards: entries that
+ * carry a String (the interner is host state), the manager entries 35-38 (the registry is host state), and every
+ * malformed entry (the host decoder words the error).  Instance ids resolve through a device hash table (id -> slot)
+ * that the call rebuilds from the session registry whenever the registry has changed since the last call.
+ * Not covered, as in cc_wire_decode: MessageBus operations and the TopicState class name stay undecoded (they escape
+ * and fail or decode exactly as before).  There is no device-resident byte-buffer form, no pipeline (one upload, one
+ * decode), and the decoded columns are not packed. */
+#define CC_WIRE_TILE_ROWS 2048
+typedef struct cc_wire_control {  /* one manager entry (kind 35-38) of the segment, fields as in cc_wire_out */
+  uint64_t row;
+  uint64_t kind;
+  uint64_t key;
+  uint64_t a;
+  uint64_t b;
+} cc_wire_control;
+typedef struct cc_wire_stats {
+  uint64_t rows;         /* entries of the call */
+  uint64_t device_rows;  /* decoded by k_wire_decode */
+  uint64_t host_rows;    /* escaped: decoded by the host fallback */
+} cc_wire_stats;
+/* h_buf / h_offsets as cc_wire_decode's buf / offsets (only bytes [offsets[0], offsets[n]) are copied; neither needs
+ * any alignment).  d_cols: device columns of n rows, each 16-byte aligned; inst, op, flags, key, a, b, aux are
+ * required, index and time are not touched.  d_iid (optional, 16-byte aligned): the instance ids.  An escaped row
+ * gets the host decoder's row; a manager entry's row therefore holds inst = max_instances, op = flags = 0 and its key /
+ * a / b, and is also returned as h_ctl[k] = {row, kind, key, a, b}, ascending by row, *ctl_count of them.  More than
+ * ctl_cap of them: CC_ERR_CAPACITY with *ctl_count = the number needed; the columns are valid, and calling again with
+ * room is harmless (interning is idempotent).  The call is synchronous on `stream`.
+ * Failure: the first failing row in row order wins, exactly as in cc_wire_decode, be it a malformed entry or an
+ * offsets violation: the same return code, cc_last_error text and *bad_row.  Device rows before it are decoded, the
+ * interner holds the Strings of the rows before it and no others, and no String key is registered
+ * (cc_handle_hashes); on success String keys are registered as cc_wire_decode does.  stats may be NULL. */
+int  cc_wire_decode_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* in, const uint8_t* h_buf,
+                              uint64_t buf_len, const uint64_t* h_offsets, uint64_t n, const cc_batch_out* d_cols,
+                              uint64_t* d_iid, cc_wire_control* h_ctl, uint64_t ctl_cap, uint64_t* ctl_count,
+                              cc_wire_stats* stats, void* stream, uint64_t* bad_row);
+/* The stage times of the engine's last decode on the device (either call), from HIP events: h_ms[0] the H2D of the
+ * bytes and offsets, h_ms[1] k_wire_decode, h_ms[2] the escape round trip (the count, and the bitmap when any row
+ * escaped, back to the host); milliseconds.  The host fallback and the patch come after and are not in it. */
+int  cc_wire_timeline(cc_engine* e, float* h_ms);
+/* Decode into engine-owned staging columns and apply rows [0, r) with cc_apply_batch, r = the first manager entry's
+ * row, or n: *h_applied = r, and when r < n, *ctl is that entry.  The host runs the manager command and calls again
+ * from row r + 1: the rows after a manager entry must see the registry it leaves behind, and only the Strings of
+ * rows <= r are interned.  h_index / h_time: the entries' log indices / times (h_time may be NULL); results and
+ * events return to the host as from cc_apply_batch_host_events (h_events may be NULL: then as cc_apply_batch_host),
+ * under its size rules, for rows [0, r).  Not pipelined: one upload, one decode, one apply. */
+int  cc_apply_wire_host(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* in, const uint8_t* h_buf,
+                        uint64_t buf_len, const uint64_t* h_offsets, uint64_t n, const uint64_t* h_index,
+                        const uint64_t* h_time, const cc_results* h_out, const cc_events* h_events,
+                        uint64_t* h_applied, cc_wire_control* ctl);
+
 /* ---- packed host batches (copycat_amd/csrc/pack.cpp, unpack.hip, host_path.hip) ---------------------------------------
  * The host-memory calls above ship index / key / a / b / aux as full u64 and inst as u32: 30 B per commit for the six
  * columns of a value batch, and the H2D of those bytes is most of a PCIe-inclusive step.  In a committed log a run of

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Decode rate of the Catalyst log: cc_wire_decode on one host thread against cc_wire_decode_to_device (k_wire_decode).
+
+The stream is c2-shaped: `--rows` InstanceCommand{CompareAndSet(expect Long, update Long)} entries of 34 bytes each over
+`--instances` open instances, built vectorised in numpy (2 B top id, 8 B instance id, 2 B op id, 2 x (3 B Long id + 8 B
+value), big-endian, the default codec).  Every entry is plain, so no row escapes to the host.  The device columns of the
+first call are checked against the host decoder's before anything is timed.
+
+Reports, as one JSON line (also written to --out): cc_wire_decode rows/s on one thread of this machine's CPU; the new
+call's total time (host wall clock around the synchronous call: offsets scan, H2D from pageable memory, kernel, escape
+count back); its H2D, kernel and escape round trip from HIP events (cc_wire_timeline); and the kernel's bytes/s over
+its algorithmic bytes (entry bytes + 8 B offset + 38 B of columns per row).  Median of --steps calls after --warmup.
+
+    python scripts/wire_rate.py [--rows 16777216] [--instances 65536] [--steps 5] [--warmup 2] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ENTRY = 34
+
+
+def cas_stream(n, instances, id_first, seed=0xCA5):
+    from copycat_amd import abi
+
+    rng = np.random.default_rng(seed)
+    e = np.zeros((n, ENTRY), np.uint8)
+    e[:, 0:2] = (1, 30)
+    e[:, 2:10] = (id_first + rng.integers(0, instances, n, dtype=np.uint64)).astype(">u8").view(np.uint8).reshape(n, 8)
+    e[:, 10:12] = (1, abi.CC_OP_VALUE_CAS)
+    for at in (12, 23):
+        e[:, at:at + 3] = (2, abi.CC_WIRE_ID_LONG >> 8, abi.CC_WIRE_ID_LONG & 255)
+        e[:, at + 3:at + 11] = rng.integers(0, 1 << 20, n, dtype=np.uint64).astype(">u8").view(np.uint8).reshape(n, 8)
+    return e.reshape(-1), np.arange(n + 1, dtype=np.uint64) * ENTRY
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rows", type=int, default=1 << 24)
+    ap.add_argument("--instances", type=int, default=65536)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(HERE), "profiles", "wire_gpu", "rate.json"))
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.dirname(HERE))
+    import torch
+
+    from copycat_amd import abi
+    from copycat_amd.engine import Engine
+    from copycat_amd.wire import Interner, WireDecoder
+
+    n, R = args.rows, args.instances
+    E = Engine(R, R, max(n, R), device=0)
+    E.resource_create_range(0, R, abi.CC_RES_VALUE)
+    E.instance_open_range(0, R, 0, 1000, 7)
+    buf, offs = cas_stream(n, R, 1000)
+    D = WireDecoder(E, Interner(1))
+
+    host_s = []
+    for k in range(2):  # the host decoder, one thread (twice: the first call also faults its output pages in)
+        t = time.perf_counter()
+        bh, iidh, kindh = D.decode(buf=buf, offsets=offs)
+        host_s.append(time.perf_counter() - t)
+    db, iid, kind, stats = D.decode_to_device(buf=buf, offsets=offs)
+    ok = stats == {"rows": n, "device_rows": n, "host_rows": 0} and not kind.any()
+    for name in ("inst", "op", "flags", "key", "a", "b", "aux"):
+        t = db.cols[name]
+        got = t.view({8: torch.int64, 4: torch.int32, 1: torch.uint8}[t.element_size()]).cpu().numpy()
+        ok = ok and np.array_equal(got.view(getattr(bh, name).dtype), getattr(bh, name))
+    ok = ok and np.array_equal(iid.view(torch.int64).cpu().numpy().view(np.uint64), iidh)
+    del db, iid
+
+    total, stage = [], []
+    for k in range(args.warmup + args.steps):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        D.decode_to_device(buf=buf, offsets=offs)
+        dt = (time.perf_counter() - t) * 1e3
+        if k >= args.warmup:
+            total.append(dt)
+            stage.append(E.wire_timeline())
+    med = statistics.median
+    h2d, kern, esc = (med(s[i] for s in stage) for i in range(3))
+    kbytes = n * (ENTRY + 8 + 38)
+    out = {"workload": "c2-shaped CompareAndSet entries, all plain", "rows": n, "instances": R, "entry_bytes": ENTRY,
+           "parity_with_cc_wire_decode": bool(ok),
+           "host_cc_wire_decode_rows_per_s_one_thread": n / min(host_s), "host_cc_wire_decode_s": round(min(host_s), 3),
+           "device_call_ms_total": round(med(total), 3), "device_call_ms_min": round(min(total), 3),
+           "device_call_ms_max": round(max(total), 3), "device_call_rows_per_s": n / (med(total) / 1e3),
+           "h2d_ms": round(h2d, 3), "h2d_bytes": int(n * ENTRY + 8 * (n + 1)),
+           "h2d_gb_per_s": round((n * ENTRY + 8 * (n + 1)) / (h2d * 1e-3) / 1e9, 2),
+           "kernel_ms": round(kern, 3), "kernel_algorithmic_bytes": int(kbytes),
+           "kernel_gb_per_s": round(kbytes / (kern * 1e-3) / 1e9, 1), "kernel_rows_per_s": n / (kern * 1e-3),
+           "escape_round_trip_ms": round(esc, 3), "kernel_longer_than_its_h2d": bool(kern > h2d),
+           "steps": args.steps, "gpu": torch.cuda.get_device_name(0)}
+    line = json.dumps(out)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
