@@ -754,19 +754,7 @@ extern "C" int cc_apply_batch_prefix(cc_engine* e, const cc_batch* c, uint64_t n
 }
 
 // ---- packed host batches (pack.cpp, unpack.hip) -----------------------------------------------------------------------
-// cc_apply_batch_host_packed is the three-stage pipeline of a PCIe-inclusive step, inside the library:
-//
-//   copy-in  (pk_in)      | H2D 0 | H2D 1 |   H2D 2   |   H2D 3   |
-//   engine   (own_stream)         | dec 0 + apply 0 | dec 1 + apply 1 | dec 2 + apply 2 | ...
-//   copy-out (pk_out)                               |   D2H 0   |     |   D2H 1   |
-//
-// A chunk is a run of whole blocks; its piece of the blob (its directory entries, then its blocks' data areas, which
-// are contiguous because offsets ascend with the block number) goes into one of two piece buffers.  The H2D of chunk
-// k + 1 is enqueued BEFORE cc_apply_batch of chunk k is called: on an engine with maps that call syncs the host, and
-// the copy must already be in flight.  Decode and apply share the engine's stream, so one decoded column set is
-// enough; there are two result sets, each copied out straight into the caller's rows [lo, hi) while the next chunk
-// is applied.  The host waits for each chunk's device-side checks (cc_sync) before it applies the next one: that is
-// what "stop at the first failing chunk" costs, one round trip per chunk of up to 16 Mi rows.
+// The decoder on its own (cc_unpack_to_device) and what the packed apply pipeline below shares with it.
 namespace {
 
 enum PkSlot : int { kHwBlob0 = kPxSlots, kHwBlob1, kHwStatus1, kHwValue1, kPkSlots };
@@ -833,183 +821,10 @@ extern "C" int cc_unpack_to_device(cc_engine* e, const void* h_blob, uint64_t by
   return CC_OK;
 }
 
-extern "C" int cc_apply_batch_host_packed(cc_engine* e, const void* h_blob, uint64_t bytes, const cc_results* hout,
-                                          const cc_events* hev, const cc_packed_opts* opts, uint64_t* h_rows_done) {
-  if (h_rows_done) *h_rows_done = 0;
-  if (!e || !hout) return set_err(CC_ERR_INVALID, "null argument");
-  if (opts && (opts->flags & ~(uint32_t)CC_PACKED_TIMELINE)) return set_err(CC_ERR_INVALID, "packed apply: unknown flag");
-  uint64_t n = 0;
-  uint32_t present = 0;
-  TRY(cc_pack_check(h_blob, bytes, &n, &present));  // (before anything is copied or launched)
-  TRY(host_events_ok(hev));
-  if (n && (!hout->status || !hout->value)) return set_err(CC_ERR_INVALID, "null argument");
-  HIPCHECK(hipSetDevice(e->device));
-  e->pk_chunks = 0;
-  if (n == 0) {
-    if (hev) *hev->count = 0;
-    return CC_OK;
-  }
-  if ((present & kPkNeed) != kPkNeed)
-    return set_err(CC_ERR_INVALID, "inst/op/flags/a/b columns and status/value outputs are required");
-  e->last_err_bits = 0;
-  hipStream_t st = e->own_stream;
-  if (st != e->last_stream) HIPCHECK(hipStreamSynchronize(e->last_stream));
-  e->last_stream = st;
-  TRY(pk_init(e));
-
-  const uint64_t kB = CC_PACK_BLOCK_ROWS;
-  uint64_t chunk = opts && opts->chunk_rows ? opts->chunk_rows : (16ull << 20);
-  chunk = std::min<uint64_t>(chunk, 1ull << 40);
-  chunk = (chunk + kB - 1) / kB * kB;
-  // whole blocks within max_batch and one extended sub-batch (an engine smaller than a block takes a block: a batch
-  // larger than max_batch then fails as it does in cc_apply_batch)
-  const uint64_t cap_rows = std::max<uint64_t>(std::min(e->cfg.max_batch, e->sub_ext) / kB * kB, kB);
-  chunk = std::min(chunk, cap_rows);
-  const uint64_t bpc = chunk / kB, nchunks = (n + chunk - 1) / chunk;
-  const bool ck = e->map_bits != 0 || hev != nullptr;  // as the parts of cc_apply_batch_host_prefix
-  if (ck) TRY(ckpt_reserve(e));
-  const bool stamps = opts && (opts->flags & CC_PACKED_TIMELINE);
-  if (stamps)
-    while (e->pk_stamp.size() < 8 * nchunks) {
-      hipEvent_t ev;
-      HIPCHECK(hipEventCreate(&ev));
-      e->pk_stamp.push_back(ev);
-    }
-  auto stamp = [&](uint64_t k, int which, hipStream_t s) -> hipError_t {
-    return stamps ? hipEventRecord(e->pk_stamp[8 * k + which], s) : hipSuccess;
-  };
-
-  const cc_pack_header* hd = (const cc_pack_header*)h_blob;
-  const uint8_t* const blob = (const uint8_t*)h_blob;
-  const cc_pack_block* const dir = (const cc_pack_block*)(blob + sizeof *hd);
-  void* piece[2] = {};
-  uint64_t piece_base[2] = {}, piece_dir[2] = {};
-  // chunk k's piece on its way: directory entries, then the data areas of its blocks
-  auto send = [&](uint64_t k) -> int {
-    const uint64_t b0 = k * bpc, b1 = std::min(hd->blocks, b0 + bpc);
-    const uint64_t lo = dir[b0].offset, hi = dir[b1 - 1].offset + dir[b1 - 1].bytes, db = (b1 - b0) * sizeof(cc_pack_block);
-    void* p = nullptr;
-    TRY(hw(e, kHwBlob0 + (int)(k & 1), db + (hi - lo), &p));
-    HIPCHECK(stamp(k, 0, e->pk_in));
-    HIPCHECK(hipMemcpyAsync(p, dir + b0, db, hipMemcpyHostToDevice, e->pk_in));
-    if (hi > lo) HIPCHECK(hipMemcpyAsync((uint8_t*)p + db, blob + lo, hi - lo, hipMemcpyHostToDevice, e->pk_in));
-    HIPCHECK(stamp(k, 1, e->pk_in));
-    HIPCHECK(hipEventRecord(e->pk_landed[k & 1], e->pk_in));
-    piece[k & 1] = p, piece_base[k & 1] = lo, piece_dir[k & 1] = db;
-    return CC_OK;
-  };
-  uint64_t ev_n = 0;  // events of the chunks so far (the failing chunk's included)
-  // every stream drained before the call returns: a copy in flight reads the caller's blob or writes its result rows
-  auto leave = [&](int rc) {
-    (void)hipStreamSynchronize(e->pk_in);
-    (void)hipStreamSynchronize(e->pk_out);
-    if (hev) *hev->count = ev_n;
-    return rc;
-  };
-  int rc = send(0);
-  if (rc) return leave(rc);
-  for (uint64_t k = 0; k < nchunks; ++k) {
-    const uint64_t lo = k * chunk, hi = std::min(n, lo + chunk), m = hi - lo;
-    const int s = (int)(k & 1);
-    if (k + 1 < nchunks && (rc = send(k + 1))) return leave(rc);
-    // decode: the wide columns of rows [lo, hi)
-    void* dcol[9] = {};
-    for (int c = 0; c < 9; ++c)
-      if (((present >> c) & 1) && (rc = hw(e, kHwCol + c, kPkEsz[c] * m, &dcol[c]))) return leave(rc);
-    void *d_status, *d_value;
-    if ((rc = hw(e, s ? kHwStatus1 : kHwStatus, m, &d_status)) || (rc = hw(e, s ? kHwValue1 : kHwValue, 8 * m, &d_value)))
-      return leave(rc);
-    hipError_t x = hipStreamWaitEvent(st, e->pk_landed[s], 0);
-    if (x == hipSuccess) x = stamp(k, 2, st);
-    if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: wait for the piece", x));
-    if (launch_unpack(unpack_args(piece[s], (const uint8_t*)piece[s] + piece_dir[s], piece_base[s], dcol, present),
-                      (uint32_t)((m + kB - 1) / kB), st))
-      return leave(set_err(CC_ERR_HIP, "unpack launch", hipGetLastError()));
-    x = stamp(k, 3, st);
-    // result set s: its copy-out of chunk k - 2 is done before it is prefilled again (sentinels as in apply_host)
-    if (x == hipSuccess && k >= 2) x = hipStreamWaitEvent(st, e->pk_drained[s], 0);
-    if (x == hipSuccess) x = hipMemsetAsync(d_status, 0xFF, m, st);
-    if (x == hipSuccess) x = hipMemsetAsync(d_value, 0xA5, 8 * m, st);
-    if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: result prefill", x));
-    // the chunk's events are appended to the host stream from the events so far on
-    uint64_t cnt = 0;
-    cc_events v{}, dev{};
-    if (hev) {
-      v = *hev;
-      const uint64_t used = std::min(ev_n, hev->capacity);
-      v.pos += used, v.target += used, v.code += used, v.src += used, v.tag += used, v.payload += used;
-      v.capacity -= used;
-      v.count = &cnt;
-    }
-    if ((rc = hw_events(e, hev ? &v : nullptr, &dev))) return leave(rc);
-    if (ck && (rc = ckpt_save(e))) return leave(rc);
-    const cc_batch d{(const uint64_t*)dcol[0], (const uint64_t*)dcol[1], (const uint32_t*)dcol[2],
-                     (const uint8_t*)dcol[3],  (const uint8_t*)dcol[4],  (const uint64_t*)dcol[5],
-                     (const uint64_t*)dcol[6], (const uint64_t*)dcol[7], (const uint64_t*)dcol[8]};
-    const cc_results r{(uint8_t*)d_status, (uint64_t*)d_value};
-    (void)stamp(k, 4, st);
-    e->last_err_bits = 0;
-    rc = cc_apply_batch(e, &d, m, &r, hev ? &dev : nullptr, st);
-    if (rc) {
-      (void)hipStreamSynchronize(st);
-      return leave(rc);
-    }
-    (void)stamp(k, 5, st);
-    const int rs = cc_sync(e);  // device-side checks (capacity, unsupported ops, time order); the stream is drained
-    const int re = hw_events_back(e, hev ? &v : nullptr, &dev);
-    for (uint64_t i = 0; hev && lo && i < std::min(cnt, v.capacity); ++i) v.pos[i] += (uint32_t)lo;
-    ev_n += cnt;
-    rc = rs ? rs : re;
-    bool rolled_back = false;
-    if (rc == CC_ERR_CAPACITY && ck) {  // a full event stream or map table region, and nothing else: not applied
-      const uint32_t bits = e->last_err_bits;
-      if (bits && !(bits & ~(kErrCapacity | kErrEvents))) {
-        const int rr = ckpt_restore(e);
-        if (rr) return leave(rr);
-        e->last_err_bits = bits;
-        rolled_back = true;
-      }
-    }
-    if (!rolled_back) {  // (a failing chunk that stays applied returns its rows, as cc_apply_batch_host does)
-      x = stamp(k, 6, e->pk_out);
-      if (x == hipSuccess) x = hipMemcpyAsync(hout->status + lo, d_status, m, hipMemcpyDeviceToHost, e->pk_out);
-      if (x == hipSuccess) x = hipMemcpyAsync(hout->value + lo, d_value, 8 * m, hipMemcpyDeviceToHost, e->pk_out);
-      if (x == hipSuccess) x = stamp(k, 7, e->pk_out);
-      if (x == hipSuccess) x = hipEventRecord(e->pk_drained[s], e->pk_out);
-      if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: result copy-out", x));
-    }
-    if (rc) return leave(rc);
-    if (h_rows_done) *h_rows_done = hi;
-    e->pk_chunks = stamps ? k + 1 : 0;
-  }
-  return leave(CC_OK);
-}
-
-extern "C" int cc_packed_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms) {
-  if (!e || !chunks || (cap && !h_ms)) return set_err(CC_ERR_INVALID, "null argument");
-  HIPCHECK(hipSetDevice(e->device));
-  *chunks = e->pk_chunks;
-  for (uint64_t k = 0; k < std::min(cap, e->pk_chunks); ++k)
-    for (int j = 0; j < 4; ++j)
-      HIPCHECK(hipEventElapsedTime(h_ms + 4 * k + j, e->pk_stamp[8 * k + 2 * j], e->pk_stamp[8 * k + 2 * j + 1]));
-  return CC_OK;
-}
-
 // ---- packed result blobs (respack.cpp, respack.hip) -------------------------------------------------------------------
-// cc_apply_batch_host_packed_results is cc_apply_batch_host_packed with a fourth stage on the engine's stream:
-//
-//   copy-in  (pk_in)      | H2D 0 | H2D 1 |      H2D 2      |
-//   engine   (own_stream)         | dec 0 + apply 0 + enc 0 | dec 1 + apply 1 + enc 1 | ...
-//   copy-out (pk_out)                                       | D2H 0 |                 | D2H 1 |
-//
-// The encoder (three launches, respack.hip) turns the chunk's wide result rows into directory entries and data areas
-// in one of two device stagings: {total word (16 B) | the chunk's directory entries | its data areas}.  Chunk k's areas
-// are placed from the blob offset where chunk k - 1's ended, which the host knows after chunk k - 1's cc_sync: the
-// encoder's total is copied into a pinned host word on the engine's stream before that sync, so it costs no round trip
-// of its own.  The copy-out then sends the directory entries and the data bytes used, and only those, to their places
-// in the caller's blob; the wide rows never leave HBM, so one wide result set is enough.  The body below follows
-// cc_apply_batch_host_packed stage by stage; that call is left as it was (it is the baseline this one is measured
-// against).
+// The encoder (three launches, respack.hip) turns wide result rows into directory entries and data areas in a device
+// staging: {total word (16 B) | directory entries | data areas}.  The encoder's total is copied into a pinned host word
+// on the same stream, so the host reads it after the synchronisation it makes anyway.
 namespace {
 
 enum RpSlot : int { kHwRes0 = kPkSlots, kHwRes1, kRpSlots };
@@ -1038,14 +853,17 @@ int rp_encode(cc_engine* e, int slot, const void* d_status, const void* d_value,
   return CC_OK;
 }
 
-void rp_header(void* h_blob, uint64_t n, uint64_t bytes) {
+// the header of a result blob or of an event blob of n rows and `bytes` bytes: they differ in magic, version and columns
+enum BlobKind { kResultBlob, kEventBlob };
+
+void blob_header(BlobKind kind, void* h_blob, uint64_t n, uint64_t bytes) {
   cc_pack_header hd{};
-  hd.magic = (uint32_t)CC_RESPACK_MAGIC;
-  hd.version = CC_RESPACK_VERSION;
+  hd.magic = kind == kResultBlob ? (uint32_t)CC_RESPACK_MAGIC : (uint32_t)CC_EVPACK_MAGIC;
+  hd.version = kind == kResultBlob ? CC_RESPACK_VERSION : CC_EVPACK_VERSION;
   hd.n = n;
   hd.blocks = rp_blocks(n);
   hd.bytes = bytes;
-  hd.present = 3;
+  hd.present = kind == kResultBlob ? 3 : 0x3F;
   hd.block_rows = CC_PACK_BLOCK_ROWS;
   std::memcpy(h_blob, &hd, sizeof hd);
 }
@@ -1063,7 +881,7 @@ extern "C" int cc_respack_from_device(cc_engine* e, const cc_results* d_results,
     return set_err(CC_ERR_CAPACITY, "result blob: the blob buffer is smaller than cc_respack_bound (*bytes = the bound)");
   }
   if (n == 0) {
-    rp_header(h_blob, 0, sizeof(cc_pack_header));
+    blob_header(kResultBlob, h_blob, 0, sizeof(cc_pack_header));
     *bytes = sizeof(cc_pack_header);
     return CC_OK;
   }
@@ -1082,216 +900,13 @@ extern "C" int cc_respack_from_device(cc_engine* e, const cc_results* d_results,
   HIPCHECK(hipMemcpyAsync((uint8_t*)h_blob + sizeof(cc_pack_header), stage + kRpHead, db + total, hipMemcpyDeviceToHost, st));
   HIPCHECK(hipStreamSynchronize(st));
   *bytes = sizeof(cc_pack_header) + db + total;
-  rp_header(h_blob, n, *bytes);
-  return CC_OK;
-}
-
-extern "C" int cc_apply_batch_host_packed_results(cc_engine* e, const void* h_blob, uint64_t bytes, void* h_res_blob,
-                                                  uint64_t res_cap, uint64_t* res_bytes, const cc_events* hev,
-                                                  const cc_packed_opts* opts, uint64_t* h_rows_done) {
-  if (h_rows_done) *h_rows_done = 0;
-  if (!e || !h_res_blob || !res_bytes) return set_err(CC_ERR_INVALID, "result blob: null argument");
-  if ((uintptr_t)h_res_blob & 15) return set_err(CC_ERR_INVALID, "result blob: the blob must be 16-byte aligned");
-  if (opts && (opts->flags & ~(uint32_t)CC_PACKED_TIMELINE)) return set_err(CC_ERR_INVALID, "packed apply: unknown flag");
-  uint64_t n = 0;
-  uint32_t present = 0;
-  TRY(cc_pack_check(h_blob, bytes, &n, &present));  // (before anything is copied or launched)
-  TRY(host_events_ok(hev));
-  uint64_t bound = 0;
-  TRY(cc_respack_bound(n, &bound));
-  if (res_cap < bound) {
-    *res_bytes = bound;
-    return set_err(CC_ERR_CAPACITY, "result blob: the blob buffer is smaller than cc_respack_bound (*res_bytes = the bound)");
-  }
-  if (n && (present & kPkNeed) != kPkNeed)
-    return set_err(CC_ERR_INVALID, "inst/op/flags/a/b columns and status/value outputs are required");
-  // from here on every return leaves a valid blob of the rows copied out so far
-  rp_header(h_res_blob, 0, sizeof(cc_pack_header));
-  *res_bytes = sizeof(cc_pack_header);
-  HIPCHECK(hipSetDevice(e->device));
-  e->rp_chunks = 0;
-  if (n == 0) {
-    if (hev) *hev->count = 0;
-    return CC_OK;
-  }
-  e->last_err_bits = 0;
-  hipStream_t st = e->own_stream;
-  if (st != e->last_stream) HIPCHECK(hipStreamSynchronize(e->last_stream));
-  e->last_stream = st;
-  TRY(pk_init(e));
-
-  const uint64_t kB = CC_PACK_BLOCK_ROWS;
-  uint64_t chunk = opts && opts->chunk_rows ? opts->chunk_rows : (16ull << 20);
-  chunk = std::min<uint64_t>(chunk, 1ull << 40);
-  chunk = (chunk + kB - 1) / kB * kB;
-  const uint64_t cap_rows = std::max<uint64_t>(std::min(e->cfg.max_batch, e->sub_ext) / kB * kB, kB);
-  chunk = std::min(chunk, cap_rows);
-  const uint64_t bpc = chunk / kB, nchunks = (n + chunk - 1) / chunk;
-  const bool ck = e->map_bits != 0 || hev != nullptr;  // as the parts of cc_apply_batch_host_prefix
-  if (ck) TRY(ckpt_reserve(e));
-  const bool stamps = opts && (opts->flags & CC_PACKED_TIMELINE);
-  if (stamps)
-    while (e->rp_stamp.size() < 10 * nchunks) {
-      hipEvent_t ev;
-      HIPCHECK(hipEventCreate(&ev));
-      e->rp_stamp.push_back(ev);
-    }
-  auto stamp = [&](uint64_t k, int which, hipStream_t s) -> hipError_t {
-    return stamps ? hipEventRecord(e->rp_stamp[10 * k + which], s) : hipSuccess;
-  };
-
-  const cc_pack_header* hd = (const cc_pack_header*)h_blob;
-  const uint8_t* const blob = (const uint8_t*)h_blob;
-  const cc_pack_block* const dir = (const cc_pack_block*)(blob + sizeof *hd);
-  void* piece[2] = {};
-  uint64_t piece_base[2] = {}, piece_dir[2] = {};
-  // chunk k's piece on its way: directory entries, then the data areas of its blocks
-  auto send = [&](uint64_t k) -> int {
-    const uint64_t b0 = k * bpc, b1 = std::min(hd->blocks, b0 + bpc);
-    const uint64_t lo = dir[b0].offset, hi = dir[b1 - 1].offset + dir[b1 - 1].bytes, db = (b1 - b0) * sizeof(cc_pack_block);
-    void* p = nullptr;
-    TRY(hw(e, kHwBlob0 + (int)(k & 1), db + (hi - lo), &p));
-    HIPCHECK(stamp(k, 0, e->pk_in));
-    HIPCHECK(hipMemcpyAsync(p, dir + b0, db, hipMemcpyHostToDevice, e->pk_in));
-    if (hi > lo) HIPCHECK(hipMemcpyAsync((uint8_t*)p + db, blob + lo, hi - lo, hipMemcpyHostToDevice, e->pk_in));
-    HIPCHECK(stamp(k, 1, e->pk_in));
-    HIPCHECK(hipEventRecord(e->pk_landed[k & 1], e->pk_in));
-    piece[k & 1] = p, piece_base[k & 1] = lo, piece_dir[k & 1] = db;
-    return CC_OK;
-  };
-  uint8_t* const res = (uint8_t*)h_res_blob;
-  // the result blob keeps the room of all n rows' directory entries; the data areas follow, chunk after chunk
-  const uint64_t res_data0 = sizeof(cc_pack_header) + rp_blocks(n) * sizeof(cc_respack_block);
-  uint64_t res_rows = 0, res_data = 0;  // rows whose results are on their way out, and their data bytes
-  uint64_t ev_n = 0;                    // events of the chunks so far (the failing chunk's included)
-  // every stream drained before the call returns: a copy in flight reads the caller's blob or writes its result blob;
-  // the host writes the header last
-  auto leave = [&](int rc) {
-    (void)hipStreamSynchronize(e->pk_in);
-    (void)hipStreamSynchronize(e->pk_out);
-    if (hev) *hev->count = ev_n;
-    *res_bytes = res_rows ? res_data0 + res_data : sizeof(cc_pack_header);
-    rp_header(res, res_rows, *res_bytes);
-    return rc;
-  };
-  int rc = send(0);
-  if (rc) return leave(rc);
-  for (uint64_t k = 0; k < nchunks; ++k) {
-    const uint64_t lo = k * chunk, hi = std::min(n, lo + chunk), m = hi - lo;
-    const int s = (int)(k & 1);
-    if (k + 1 < nchunks && (rc = send(k + 1))) return leave(rc);
-    // decode: the wide columns of rows [lo, hi)
-    void* dcol[9] = {};
-    for (int c = 0; c < 9; ++c)
-      if (((present >> c) & 1) && (rc = hw(e, kHwCol + c, kPkEsz[c] * m, &dcol[c]))) return leave(rc);
-    void *d_status, *d_value;
-    if ((rc = hw(e, kHwStatus, m, &d_status)) || (rc = hw(e, kHwValue, 8 * m, &d_value))) return leave(rc);
-    hipError_t x = hipStreamWaitEvent(st, e->pk_landed[s], 0);
-    if (x == hipSuccess) x = stamp(k, 2, st);
-    if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: wait for the piece", x));
-    if (launch_unpack(unpack_args(piece[s], (const uint8_t*)piece[s] + piece_dir[s], piece_base[s], dcol, present),
-                      (uint32_t)((m + kB - 1) / kB), st))
-      return leave(set_err(CC_ERR_HIP, "unpack launch", hipGetLastError()));
-    x = stamp(k, 3, st);
-    // the wide rows stay in HBM (sentinels as in apply_host); chunk k - 1's encode has read them on this stream
-    if (x == hipSuccess) x = hipMemsetAsync(d_status, 0xFF, m, st);
-    if (x == hipSuccess) x = hipMemsetAsync(d_value, 0xA5, 8 * m, st);
-    if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: result prefill", x));
-    // the chunk's events are appended to the host stream from the events so far on
-    uint64_t cnt = 0;
-    cc_events v{}, dev{};
-    if (hev) {
-      v = *hev;
-      const uint64_t used = std::min(ev_n, hev->capacity);
-      v.pos += used, v.target += used, v.code += used, v.src += used, v.tag += used, v.payload += used;
-      v.capacity -= used;
-      v.count = &cnt;
-    }
-    if ((rc = hw_events(e, hev ? &v : nullptr, &dev))) return leave(rc);
-    if (ck && (rc = ckpt_save(e))) return leave(rc);
-    const cc_batch d{(const uint64_t*)dcol[0], (const uint64_t*)dcol[1], (const uint32_t*)dcol[2],
-                     (const uint8_t*)dcol[3],  (const uint8_t*)dcol[4],  (const uint64_t*)dcol[5],
-                     (const uint64_t*)dcol[6], (const uint64_t*)dcol[7], (const uint64_t*)dcol[8]};
-    const cc_results r{(uint8_t*)d_status, (uint64_t*)d_value};
-    (void)stamp(k, 4, st);
-    e->last_err_bits = 0;
-    rc = cc_apply_batch(e, &d, m, &r, hev ? &dev : nullptr, st);
-    if (rc) {
-      (void)hipStreamSynchronize(st);
-      return leave(rc);
-    }
-    (void)stamp(k, 5, st);
-    // encode into staging s once its copy-out of chunk k - 2 is done; the total comes back with the chunk's checks
-    uint8_t* stage = nullptr;
-    if (k >= 2 && (x = hipStreamWaitEvent(st, e->pk_drained[s], 0)) != hipSuccess)
-      return leave(set_err(CC_ERR_HIP, "packed apply: wait for the result staging", x));
-    (void)stamp(k, 6, st);
-    if ((rc = rp_encode(e, kHwRes0 + s, d_status, d_value, m, res_data0 + res_data, st, &stage))) {
-      (void)hipStreamSynchronize(st);
-      return leave(rc);
-    }
-    (void)stamp(k, 7, st);
-    const int rs = cc_sync(e);  // device-side checks (capacity, unsupported ops, time order); the stream is drained
-    const int re = hw_events_back(e, hev ? &v : nullptr, &dev);
-    for (uint64_t i = 0; hev && lo && i < std::min(cnt, v.capacity); ++i) v.pos[i] += (uint32_t)lo;
-    ev_n += cnt;
-    rc = rs ? rs : re;
-    bool rolled_back = false;
-    if (rc == CC_ERR_CAPACITY && ck) {  // a full event stream or map table region, and nothing else: not applied
-      const uint32_t bits = e->last_err_bits;
-      if (bits && !(bits & ~(kErrCapacity | kErrEvents))) {
-        const int rr = ckpt_restore(e);
-        if (rr) return leave(rr);
-        e->last_err_bits = bits;
-        rolled_back = true;
-      }
-    }
-    if (!rolled_back) {  // (a failing chunk that stays applied returns its rows, as cc_apply_batch_host does)
-      const uint64_t total = *e->rp_pin, db = rp_blocks(m) * sizeof(cc_respack_block);
-      if (total > 9 * m + 32)
-        return leave(set_err(CC_ERR_STATE, "internal check: the result blob encoder wrote past its bound"));
-      x = stamp(k, 8, e->pk_out);
-      if (x == hipSuccess)
-        x = hipMemcpyAsync(res + sizeof(cc_pack_header) + (lo / kB) * sizeof(cc_respack_block), stage + kRpHead, db,
-                           hipMemcpyDeviceToHost, e->pk_out);
-      if (x == hipSuccess && total)
-        x = hipMemcpyAsync(res + res_data0 + res_data, stage + kRpHead + db, total, hipMemcpyDeviceToHost, e->pk_out);
-      if (x == hipSuccess) x = stamp(k, 9, e->pk_out);
-      if (x == hipSuccess) x = hipEventRecord(e->pk_drained[s], e->pk_out);
-      if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: result blob copy-out", x));
-      res_rows = hi, res_data += total;
-    }
-    if (rc) return leave(rc);
-    if (h_rows_done) *h_rows_done = hi;
-    e->rp_chunks = stamps ? k + 1 : 0;
-  }
-  return leave(CC_OK);
-}
-
-extern "C" int cc_packed_results_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms) {
-  if (!e || !chunks || (cap && !h_ms)) return set_err(CC_ERR_INVALID, "null argument");
-  HIPCHECK(hipSetDevice(e->device));
-  *chunks = e->rp_chunks;
-  for (uint64_t k = 0; k < std::min(cap, e->rp_chunks); ++k)
-    for (int j = 0; j < 5; ++j)
-      HIPCHECK(hipEventElapsedTime(h_ms + 5 * k + j, e->rp_stamp[10 * k + 2 * j], e->rp_stamp[10 * k + 2 * j + 1]));
+  blob_header(kResultBlob, h_blob, n, *bytes);
   return CC_OK;
 }
 
 // ---- packed event blobs (evpack.cpp, evpack.hip) ----------------------------------------------------------------------
-// cc_apply_batch_host_packed_events is cc_apply_batch_host_packed_results with the event stream kept in HBM:
-//
-//   copy-in  (pk_in)      | H2D 0 | H2D 1 |      H2D 2      |
-//   engine   (own_stream)         | dec 0 + apply 0 + enc 0 + shift 0 | dec 1 + apply 1 + enc 1 + shift 1 | ... | ev enc | ev D2H |
-//   copy-out (pk_out)                                       | D2H 0 |                             | D2H 1 |
-//
-// Chunk k's events are appended to engine-owned device columns after those of the chunks before (cc_apply_batch
-// writes them there), its count comes back in a pinned word with the chunk's checks, and its pos values are shifted to
-// batch rows by a kernel.  The blob is encoded once, after the last chunk, and leaves in one D2H: the directory's
-// length, and with it the offset of every data area, is known only with the last chunk's count, so a block sent earlier
-// would have no final place in the caller's blob (the result blob knows its row count up front).  The body follows
-// cc_apply_batch_host_packed_results stage by stage; that call is left as it was (the baseline this one is measured
-// against).
+// Device event columns (the caller's, or the engine-owned ones the packed apply pipeline accumulates a call's events
+// in) encoded into one staging and sent in one D2H.
 namespace {
 
 enum EpSlot : int { kHwEvAcc = kRpSlots, kHwEvStage, kEpSlots };
@@ -1315,18 +930,6 @@ int ep_columns(cc_engine* e, uint64_t cap, cc_events* d) {
   d->tag = q;
   d->capacity = cap;
   return CC_OK;
-}
-
-void ep_header(void* h_blob, uint64_t n, uint64_t bytes) {
-  cc_pack_header hd{};
-  hd.magic = (uint32_t)CC_EVPACK_MAGIC;
-  hd.version = CC_EVPACK_VERSION;
-  hd.n = n;
-  hd.blocks = rp_blocks(n);
-  hd.bytes = bytes;
-  hd.present = 0x3F;
-  hd.block_rows = CC_PACK_BLOCK_ROWS;
-  std::memcpy(h_blob, &hd, sizeof hd);
 }
 
 int ep_pin(cc_engine* e) {
@@ -1372,7 +975,7 @@ int ep_encode(cc_engine* e, const cc_events* d, uint64_t m, void* h_blob, hipStr
   }
   HIPCHECK(mark(3));
   HIPCHECK(hipStreamSynchronize(st));
-  ep_header(h_blob, m, *bytes);
+  blob_header(kEventBlob, h_blob, m, *bytes);
   return CC_OK;
 }
 
@@ -1404,74 +1007,121 @@ extern "C" int cc_evpack_from_device(cc_engine* e, const cc_events* d, void* h_b
   return CC_OK;
 }
 
-extern "C" int cc_apply_batch_host_packed_events(cc_engine* e, const void* h_blob, uint64_t bytes, void* h_res_blob,
-                                                 uint64_t res_cap, uint64_t* res_bytes, void* h_ev_blob,
-                                                 uint64_t ev_capacity, uint64_t ev_cap_bytes, uint64_t* ev_bytes,
-                                                 uint64_t* ev_count, const cc_packed_opts* opts, uint64_t* h_rows_done) {
-  if (h_rows_done) *h_rows_done = 0;
-  if (!e || !h_res_blob || !res_bytes) return set_err(CC_ERR_INVALID, "result blob: null argument");
-  if ((uintptr_t)h_res_blob & 15) return set_err(CC_ERR_INVALID, "result blob: the blob must be 16-byte aligned");
-  if (!h_ev_blob || !ev_bytes || !ev_count) return set_err(CC_ERR_INVALID, "event blob: null argument");
-  if ((uintptr_t)h_ev_blob & 15) return set_err(CC_ERR_INVALID, "event blob: the blob must be 16-byte aligned");
-  if (opts && (opts->flags & ~(uint32_t)CC_PACKED_TIMELINE)) return set_err(CC_ERR_INVALID, "packed apply: unknown flag");
-  uint64_t n = 0;
-  uint32_t present = 0;
-  TRY(cc_pack_check(h_blob, bytes, &n, &present));  // (before anything is copied or launched)
-  uint64_t bound = 0;
-  TRY(cc_respack_bound(n, &bound));
-  if (res_cap < bound) {
-    *res_bytes = bound;
-    return set_err(CC_ERR_CAPACITY, "result blob: the blob buffer is smaller than cc_respack_bound (*res_bytes = the bound)");
+// ---- the packed apply pipeline -------------------------------------------------------------------------------------------
+// cc_apply_batch_host_packed, cc_apply_batch_host_packed_results and cc_apply_batch_host_packed_events are one chunked,
+// three-stream pipeline of a PCIe-inclusive step inside the library (pk_run); each entry point checks its own arguments,
+// says where results and events go (PkSink) and runs it:
+//
+//   copy-in  (pk_in)      | H2D 0 | H2D 1 |        H2D 2        |
+//   engine   (own_stream)         | dec 0 + apply 0 [+ enc 0] | dec 1 + apply 1 [+ enc 1] | ... [| ev enc | ev D2H |]
+//   copy-out (pk_out)                                         | D2H 0 |                   | D2H 1 |
+//
+// A chunk is a run of whole blocks; its piece of the blob (its directory entries, then its blocks' data areas, which
+// are contiguous because offsets ascend with the block number) goes into one of two piece buffers.  The H2D of chunk
+// k + 1 is enqueued BEFORE cc_apply_batch of chunk k is called: on an engine with maps that call syncs the host, and
+// the copy must already be in flight.  Decode and apply share the engine's stream, so one decoded column set is
+// enough.  The host waits for each chunk's device-side checks (cc_sync) before it applies the next one: that is what
+// "stop at the first failing chunk" costs, one round trip per chunk of up to 16 Mi rows.  On an engine with maps or
+// with an event sink every chunk runs under a device checkpoint (as the parts of cc_apply_batch_host_prefix): a chunk
+// that fails on a full event stream or map table region, and on nothing else, is rolled back and copied out nowhere;
+// a chunk that fails for any other reason stays applied and its rows are copied out before the call returns.
+//
+// What the sinks change:
+//
+//   results  wide    two wide result sets (k & 1), each copied out straight into the caller's rows [lo, hi) while the
+//                    next chunk is applied; set s is prefilled again only after its copy-out of chunk k - 2.
+//                    Timeline: 8 stamps per chunk (H2D, decode, apply, D2H).
+//            blob    one wide set, which never leaves HBM: the encoder (rp_encode) writes the chunk's directory entries
+//                    and data areas into one of two stagings (k & 1) once that staging's copy-out of chunk k - 2 is
+//                    done.  Chunk k's areas are placed from the blob offset where chunk k - 1's ended, which the host
+//                    knows after chunk k - 1's cc_sync.  The copy-out sends the directory entries and the data bytes
+//                    used, and only those, to their places in the caller's blob; the host writes the header last.
+//                    Timeline: 10 stamps per chunk (H2D, decode, apply, encode, D2H).
+//   events   none    nothing published (a publishing op fails the chunk); a checkpoint only on an engine with maps.
+//            host    the chunk's events go to staging columns and from there, after the chunk's checks, to the caller's
+//                    columns behind the events so far (hw_events / hw_events_back); pos is shifted to batch rows on
+//                    the host.
+//            device  the chunk's events are appended to engine-owned device columns behind those of the chunks before,
+//                    the count comes back in a pinned word with the chunk's checks, and pos is shifted by a kernel once
+//                    the chunk is kept.  The blob is encoded once, after the last chunk, and leaves in one D2H: its
+//                    directory's length, and with it the offset of every data area, is known only with the last
+//                    chunk's count (the result blob knows its row count up front).
+namespace {
+
+enum PkResults { kResWide, kResBlob };
+enum PkEvents { kEvNone, kEvHost, kEvDevice };
+
+// where a call's results and events go; the fields of the sinks not in use stay null
+struct PkSink {
+  PkResults results;
+  PkEvents events;
+  // kResWide: the caller's rows
+  const cc_results* hout;
+  // kResBlob: the caller's blob, with room for cc_respack_bound(n) bytes, and where its size goes
+  uint8_t* res;
+  uint64_t* res_bytes;
+  // kEvHost: the caller's columns and count
+  const cc_events* hev;
+  // kEvDevice: the caller's blob, with room for cc_evpack_bound(ev_capacity) bytes, where its size goes, and where the
+  // events published go (the failing chunk's included, as kEvHost's count)
+  void* ev_blob;
+  uint64_t ev_capacity;
+  uint64_t* ev_bytes;
+  uint64_t* ev_count;
+  // CC_PACKED_TIMELINE: the stamps of the last call of this kind, and its chunks whose stamps are all recorded (each
+  // kind of call keeps its own, so its timeline call reports the last call of its kind)
+  std::vector<hipEvent_t>* stamp;
+  uint64_t* chunks;
+};
+
+void ev_advance(cc_events* v, uint64_t used) {
+  v->pos += used, v->target += used, v->code += used, v->src += used, v->tag += used, v->payload += used;
+  v->capacity -= used;
+}
+
+int more_stamps(std::vector<hipEvent_t>* v, uint64_t want) {
+  while (v->size() < want) {
+    hipEvent_t ev;
+    HIPCHECK(hipEventCreate(&ev));
+    v->push_back(ev);
   }
-  TRY(cc_evpack_bound(ev_capacity, &bound));
-  if (ev_cap_bytes < bound) {
-    *ev_bytes = bound;
-    return set_err(CC_ERR_CAPACITY, "event blob: the blob buffer is smaller than cc_evpack_bound (*ev_bytes = the bound)");
-  }
-  if (n && (present & kPkNeed) != kPkNeed)
-    return set_err(CC_ERR_INVALID, "inst/op/flags/a/b columns and status/value outputs are required");
-  // from here on every return leaves a valid result blob of the rows copied out so far and a valid event blob
-  rp_header(h_res_blob, 0, sizeof(cc_pack_header));
-  *res_bytes = sizeof(cc_pack_header);
-  ep_header(h_ev_blob, 0, sizeof(cc_pack_header));
-  *ev_bytes = sizeof(cc_pack_header);
-  *ev_count = 0;
-  HIPCHECK(hipSetDevice(e->device));
-  e->ep_chunks = 0;
-  if (n == 0) return CC_OK;
+  return CC_OK;
+}
+
+// rows [0, n) of a checked blob (n > 0, its columns `present`) applied chunk by chunk
+int pk_run(cc_engine* e, const void* h_blob, uint64_t n, uint32_t present, const cc_packed_opts* opts, const PkSink& o,
+           uint64_t* h_rows_done) {
+  const bool res_blob = o.results == kResBlob, ev_host = o.events == kEvHost, ev_dev = o.events == kEvDevice;
   e->last_err_bits = 0;
   hipStream_t st = e->own_stream;
   if (st != e->last_stream) HIPCHECK(hipStreamSynchronize(e->last_stream));
   e->last_stream = st;
   TRY(pk_init(e));
-  TRY(ep_pin(e));
+  if (ev_dev) TRY(ep_pin(e));
 
   const uint64_t kB = CC_PACK_BLOCK_ROWS;
   uint64_t chunk = opts && opts->chunk_rows ? opts->chunk_rows : (16ull << 20);
   chunk = std::min<uint64_t>(chunk, 1ull << 40);
   chunk = (chunk + kB - 1) / kB * kB;
+  // whole blocks within max_batch and one extended sub-batch (an engine smaller than a block takes a block: a batch
+  // larger than max_batch then fails as it does in cc_apply_batch)
   const uint64_t cap_rows = std::max<uint64_t>(std::min(e->cfg.max_batch, e->sub_ext) / kB * kB, kB);
   chunk = std::min(chunk, cap_rows);
   const uint64_t bpc = chunk / kB, nchunks = (n + chunk - 1) / chunk;
-  TRY(ckpt_reserve(e));  // (an event stream: every chunk runs under a device checkpoint)
+  const bool ck = e->map_bits != 0 || o.events != kEvNone;  // as the parts of cc_apply_batch_host_prefix
+  if (ck) TRY(ckpt_reserve(e));
   const bool stamps = opts && (opts->flags & CC_PACKED_TIMELINE);
+  const uint64_t per = res_blob ? 10 : 8;  // stamps per chunk; the copy-out's are the last two
   if (stamps) {
-    while (e->ep_stamp.size() < 10 * nchunks) {
-      hipEvent_t ev;
-      HIPCHECK(hipEventCreate(&ev));
-      e->ep_stamp.push_back(ev);
-    }
-    while (e->ep_call_stamp.size() < 4) {
-      hipEvent_t ev;
-      HIPCHECK(hipEventCreate(&ev));
-      e->ep_call_stamp.push_back(ev);
-    }
+    TRY(more_stamps(o.stamp, per * nchunks));
+    if (ev_dev) TRY(more_stamps(&e->ep_call_stamp, 4));
   }
-  auto stamp = [&](uint64_t k, int which, hipStream_t s) -> hipError_t {
-    return stamps ? hipEventRecord(e->ep_stamp[10 * k + which], s) : hipSuccess;
+  auto stamp = [&](uint64_t k, uint64_t which, hipStream_t s) -> hipError_t {
+    return stamps ? hipEventRecord((*o.stamp)[per * k + which], s) : hipSuccess;
   };
-  cc_events acc{};  // the call's events, in HBM
-  TRY(ep_columns(e, ev_capacity, &acc));
+  cc_events acc{};  // kEvDevice: the call's events, in HBM
+  if (ev_dev) TRY(ep_columns(e, o.ev_capacity, &acc));
+  const uint64_t ev_cap = ev_host ? o.hev->capacity : o.ev_capacity;
 
   const cc_pack_header* hd = (const cc_pack_header*)h_blob;
   const uint8_t* const blob = (const uint8_t*)h_blob;
@@ -1492,23 +1142,28 @@ extern "C" int cc_apply_batch_host_packed_events(cc_engine* e, const void* h_blo
     piece[k & 1] = p, piece_base[k & 1] = lo, piece_dir[k & 1] = db;
     return CC_OK;
   };
-  uint8_t* const res = (uint8_t*)h_res_blob;
+  // the result blob keeps the room of all n rows' directory entries; the data areas follow, chunk after chunk
   const uint64_t res_data0 = sizeof(cc_pack_header) + rp_blocks(n) * sizeof(cc_respack_block);
   uint64_t res_rows = 0, res_data = 0;  // rows whose results are on their way out, and their data bytes
   uint64_t ev_n = 0;                    // events of the chunks so far (the failing chunk's included)
-  uint64_t ev_kept = 0;                 // events of the chunks fully applied: the blob's
-  // every stream drained before the call returns; the event blob is encoded and sent here, the headers go last
+  uint64_t ev_kept = 0;                 // events of the chunks fully applied: the event blob's
+  // every stream drained before the call returns: a copy in flight reads the caller's blob or writes its results.  The
+  // host writes the result blob's header last; the event blob is encoded and sent here
   auto leave = [&](int rc) {
     (void)hipStreamSynchronize(e->pk_in);
     (void)hipStreamSynchronize(e->pk_out);
-    *ev_count = ev_n;
-    *res_bytes = res_rows ? res_data0 + res_data : sizeof(cc_pack_header);
-    rp_header(res, res_rows, *res_bytes);
+    if (ev_host) *o.hev->count = ev_n;
+    if (ev_dev) *o.ev_count = ev_n;
+    if (res_blob) {
+      *o.res_bytes = res_rows ? res_data0 + res_data : sizeof(cc_pack_header);
+      blob_header(kResultBlob, o.res, res_rows, *o.res_bytes);
+    }
+    if (!ev_dev) return rc;
     const char* const why = rc ? cc_last_error() : nullptr;
     const std::string kept = why ? why : "";
-    const int re = ep_encode(e, &acc, ev_kept, h_ev_blob, st, ev_bytes, stamps ? e->ep_call_stamp.data() : nullptr);
-    if (re) {  // (the header-only blob written above stands)
-      *ev_bytes = sizeof(cc_pack_header);
+    const int re = ep_encode(e, &acc, ev_kept, o.ev_blob, st, o.ev_bytes, stamps ? e->ep_call_stamp.data() : nullptr);
+    if (re) {  // (the header-only blob the entry point wrote stands)
+      *o.ev_bytes = sizeof(cc_pack_header);
       if (rc) (void)set_err(rc, kept.c_str());
     }
     return rc ? rc : re;
@@ -1523,8 +1178,10 @@ extern "C" int cc_apply_batch_host_packed_events(cc_engine* e, const void* h_blo
     void* dcol[9] = {};
     for (int c = 0; c < 9; ++c)
       if (((present >> c) & 1) && (rc = hw(e, kHwCol + c, kPkEsz[c] * m, &dcol[c]))) return leave(rc);
+    const bool set1 = !res_blob && s;  // (only the wide sink has a second wide set)
     void *d_status, *d_value;
-    if ((rc = hw(e, kHwStatus, m, &d_status)) || (rc = hw(e, kHwValue, 8 * m, &d_value))) return leave(rc);
+    if ((rc = hw(e, set1 ? kHwStatus1 : kHwStatus, m, &d_status)) || (rc = hw(e, set1 ? kHwValue1 : kHwValue, 8 * m, &d_value)))
+      return leave(rc);
     hipError_t x = hipStreamWaitEvent(st, e->pk_landed[s], 0);
     if (x == hipSuccess) x = stamp(k, 2, st);
     if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: wait for the piece", x));
@@ -1532,55 +1189,72 @@ extern "C" int cc_apply_batch_host_packed_events(cc_engine* e, const void* h_blo
                       (uint32_t)((m + kB - 1) / kB), st))
       return leave(set_err(CC_ERR_HIP, "unpack launch", hipGetLastError()));
     x = stamp(k, 3, st);
-    // the wide rows stay in HBM (sentinels as in apply_host); chunk k - 1's encode has read them on this stream
+    // sentinels as in apply_host.  Wide: result set s is prefilled again once its copy-out of chunk k - 2 is done.  Blob:
+    // chunk k - 1's encode has read the one set on this stream
+    if (x == hipSuccess && !res_blob && k >= 2) x = hipStreamWaitEvent(st, e->pk_drained[s], 0);
     if (x == hipSuccess) x = hipMemsetAsync(d_status, 0xFF, m, st);
     if (x == hipSuccess) x = hipMemsetAsync(d_value, 0xA5, 8 * m, st);
-    // the chunk's events are appended to the device columns from the events so far on
-    const uint64_t used = std::min(ev_n, ev_capacity);
-    cc_events dev = acc;
-    dev.pos += used, dev.target += used, dev.code += used, dev.src += used, dev.tag += used, dev.payload += used;
-    dev.capacity -= used;
-    if (x == hipSuccess) x = hipMemsetAsync(dev.count, 0, sizeof(uint64_t), st);
+    // the chunk's events are appended behind the events so far, in the device columns or in the host stream
+    const uint64_t used = std::min(ev_n, ev_cap);
+    uint64_t cnt = 0;
+    cc_events v{}, dev{};
+    if (ev_dev) {
+      dev = acc;
+      ev_advance(&dev, used);
+      if (x == hipSuccess) x = hipMemsetAsync(dev.count, 0, sizeof(uint64_t), st);
+    }
     if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: result prefill", x));
-    if ((rc = ckpt_save(e))) return leave(rc);
+    if (ev_host) {
+      v = *o.hev;
+      ev_advance(&v, used);
+      v.count = &cnt;
+      if ((rc = hw_events(e, &v, &dev))) return leave(rc);
+    }
+    if (ck && (rc = ckpt_save(e))) return leave(rc);
     const cc_batch d{(const uint64_t*)dcol[0], (const uint64_t*)dcol[1], (const uint32_t*)dcol[2],
                      (const uint8_t*)dcol[3],  (const uint8_t*)dcol[4],  (const uint64_t*)dcol[5],
                      (const uint64_t*)dcol[6], (const uint64_t*)dcol[7], (const uint64_t*)dcol[8]};
     const cc_results r{(uint8_t*)d_status, (uint64_t*)d_value};
     (void)stamp(k, 4, st);
     e->last_err_bits = 0;
-    rc = cc_apply_batch(e, &d, m, &r, &dev, st);
+    rc = cc_apply_batch(e, &d, m, &r, o.events != kEvNone ? &dev : nullptr, st);
     if (rc) {
       (void)hipStreamSynchronize(st);
       return leave(rc);
     }
     (void)stamp(k, 5, st);
-    // encode into staging s once its copy-out of chunk k - 2 is done; the total comes back with the chunk's checks
     uint8_t* stage = nullptr;
-    if (k >= 2 && (x = hipStreamWaitEvent(st, e->pk_drained[s], 0)) != hipSuccess)
-      return leave(set_err(CC_ERR_HIP, "packed apply: wait for the result staging", x));
-    (void)stamp(k, 6, st);
-    if ((rc = rp_encode(e, kHwRes0 + s, d_status, d_value, m, res_data0 + res_data, st, &stage))) {
-      (void)hipStreamSynchronize(st);
-      return leave(rc);
+    if (res_blob) {  // encode into staging s once its copy-out of chunk k - 2 is done; the total comes back with the checks
+      if (k >= 2 && (x = hipStreamWaitEvent(st, e->pk_drained[s], 0)) != hipSuccess)
+        return leave(set_err(CC_ERR_HIP, "packed apply: wait for the result staging", x));
+      (void)stamp(k, 6, st);
+      if ((rc = rp_encode(e, kHwRes0 + s, d_status, d_value, m, res_data0 + res_data, st, &stage))) {
+        (void)hipStreamSynchronize(st);
+        return leave(rc);
+      }
+      (void)stamp(k, 7, st);
     }
-    (void)stamp(k, 7, st);
-    // the chunk's event count comes back with its checks too
-    if ((x = hipMemcpyAsync(e->ep_pin, dev.count, sizeof(uint64_t), hipMemcpyDeviceToHost, st)) != hipSuccess) {
+    // (the device columns' count of the chunk comes back with its checks too)
+    if (ev_dev && (x = hipMemcpyAsync(e->ep_pin, dev.count, sizeof(uint64_t), hipMemcpyDeviceToHost, st)) != hipSuccess) {
       (void)hipStreamSynchronize(st);
       return leave(set_err(CC_ERR_HIP, "packed apply: event count read-back", x));
     }
     const int rs = cc_sync(e);  // device-side checks (capacity, unsupported ops, time order); the stream is drained
-    const uint64_t cnt = e->ep_pin[0];
     int re = CC_OK;
-    if (cnt > dev.capacity) {
-      e->last_err_bits |= kErrEvents;  // (a full event stream, like a full max_events arena)
-      re = set_err(CC_ERR_CAPACITY, "more events than the host event stream holds");
+    if (ev_host) {
+      re = hw_events_back(e, &v, &dev);
+      for (uint64_t i = 0; lo && i < std::min(cnt, v.capacity); ++i) v.pos[i] += (uint32_t)lo;
+    } else if (ev_dev) {
+      cnt = e->ep_pin[0];
+      if (cnt > dev.capacity) {
+        e->last_err_bits |= kErrEvents;  // (a full event stream, like a full max_events arena)
+        re = set_err(CC_ERR_CAPACITY, "more events than the host event stream holds");
+      }
     }
     ev_n += cnt;
     rc = rs ? rs : re;
     bool rolled_back = false;
-    if (rc == CC_ERR_CAPACITY) {  // a full event stream or map table region, and nothing else: not applied
+    if (rc == CC_ERR_CAPACITY && ck) {  // a full event stream or map table region, and nothing else: not applied
       const uint32_t bits = e->last_err_bits;
       if (bits && !(bits & ~(kErrCapacity | kErrEvents))) {
         const int rr = ckpt_restore(e);
@@ -1590,29 +1264,170 @@ extern "C" int cc_apply_batch_host_packed_events(cc_engine* e, const void* h_blo
       }
     }
     if (!rolled_back) {  // (a failing chunk that stays applied returns its rows, as cc_apply_batch_host does)
-      const uint64_t total = *e->rp_pin, db = rp_blocks(m) * sizeof(cc_respack_block);
-      if (total > 9 * m + 32)
-        return leave(set_err(CC_ERR_STATE, "internal check: the result blob encoder wrote past its bound"));
-      x = stamp(k, 8, e->pk_out);
-      if (x == hipSuccess)
-        x = hipMemcpyAsync(res + sizeof(cc_pack_header) + (lo / kB) * sizeof(cc_respack_block), stage + kRpHead, db,
-                           hipMemcpyDeviceToHost, e->pk_out);
-      if (x == hipSuccess && total)
-        x = hipMemcpyAsync(res + res_data0 + res_data, stage + kRpHead + db, total, hipMemcpyDeviceToHost, e->pk_out);
-      if (x == hipSuccess) x = stamp(k, 9, e->pk_out);
+      uint64_t total = 0;
+      if (res_blob) {  // the directory entries to their place, the data bytes used behind those of the chunks before
+        const uint64_t db = rp_blocks(m) * sizeof(cc_respack_block);
+        total = *e->rp_pin;
+        if (total > 9 * m + 32)
+          return leave(set_err(CC_ERR_STATE, "internal check: the result blob encoder wrote past its bound"));
+        x = stamp(k, per - 2, e->pk_out);
+        if (x == hipSuccess)
+          x = hipMemcpyAsync(o.res + sizeof(cc_pack_header) + (lo / kB) * sizeof(cc_respack_block), stage + kRpHead, db,
+                             hipMemcpyDeviceToHost, e->pk_out);
+        if (x == hipSuccess && total)
+          x = hipMemcpyAsync(o.res + res_data0 + res_data, stage + kRpHead + db, total, hipMemcpyDeviceToHost, e->pk_out);
+      } else {
+        x = stamp(k, per - 2, e->pk_out);
+        if (x == hipSuccess) x = hipMemcpyAsync(o.hout->status + lo, d_status, m, hipMemcpyDeviceToHost, e->pk_out);
+        if (x == hipSuccess) x = hipMemcpyAsync(o.hout->value + lo, d_value, 8 * m, hipMemcpyDeviceToHost, e->pk_out);
+      }
+      if (x == hipSuccess) x = stamp(k, per - 1, e->pk_out);
       if (x == hipSuccess) x = hipEventRecord(e->pk_drained[s], e->pk_out);
-      if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: result blob copy-out", x));
+      if (x != hipSuccess)
+        return leave(set_err(CC_ERR_HIP, res_blob ? "packed apply: result blob copy-out" : "packed apply: result copy-out", x));
       res_rows = hi, res_data += total;
     }
     if (rc) return leave(rc);
-    // the chunk is applied: its events stay, their rows as batch positions
-    if (lo && cnt && launch_ev_shift(dev.pos, cnt, (uint32_t)lo, st))
+    // the chunk is kept: its events in the device columns stay, their rows as batch positions
+    if (ev_dev && lo && cnt && launch_ev_shift(dev.pos, cnt, (uint32_t)lo, st))
       return leave(set_err(CC_ERR_HIP, "event row shift launch", hipGetLastError()));
     ev_kept = ev_n;
     if (h_rows_done) *h_rows_done = hi;
-    e->ep_chunks = stamps ? k + 1 : 0;
+    *o.chunks = stamps ? k + 1 : 0;
   }
   return leave(CC_OK);
+}
+
+// the two checks of the caller's result blob buffer that both result-blob calls make (other checks lie between them)
+int res_blob_ok(const void* h_res_blob, const uint64_t* res_bytes) {
+  if (!h_res_blob || !res_bytes) return set_err(CC_ERR_INVALID, "result blob: null argument");
+  if ((uintptr_t)h_res_blob & 15) return set_err(CC_ERR_INVALID, "result blob: the blob must be 16-byte aligned");
+  return CC_OK;
+}
+
+int res_blob_room(uint64_t n, uint64_t res_cap, uint64_t* res_bytes) {
+  uint64_t bound = 0;
+  TRY(cc_respack_bound(n, &bound));
+  if (res_cap < bound) {
+    *res_bytes = bound;
+    return set_err(CC_ERR_CAPACITY, "result blob: the blob buffer is smaller than cc_respack_bound (*res_bytes = the bound)");
+  }
+  return CC_OK;
+}
+
+}  // namespace
+
+extern "C" int cc_apply_batch_host_packed(cc_engine* e, const void* h_blob, uint64_t bytes, const cc_results* hout,
+                                          const cc_events* hev, const cc_packed_opts* opts, uint64_t* h_rows_done) {
+  if (h_rows_done) *h_rows_done = 0;
+  if (!e || !hout) return set_err(CC_ERR_INVALID, "null argument");
+  if (opts && (opts->flags & ~(uint32_t)CC_PACKED_TIMELINE)) return set_err(CC_ERR_INVALID, "packed apply: unknown flag");
+  uint64_t n = 0;
+  uint32_t present = 0;
+  TRY(cc_pack_check(h_blob, bytes, &n, &present));  // (before anything is copied or launched)
+  TRY(host_events_ok(hev));
+  if (n && (!hout->status || !hout->value)) return set_err(CC_ERR_INVALID, "null argument");
+  HIPCHECK(hipSetDevice(e->device));
+  e->pk_chunks = 0;
+  if (n == 0) {
+    if (hev) *hev->count = 0;
+    return CC_OK;
+  }
+  if ((present & kPkNeed) != kPkNeed)
+    return set_err(CC_ERR_INVALID, "inst/op/flags/a/b columns and status/value outputs are required");
+  PkSink o{};
+  o.results = kResWide, o.hout = hout;
+  o.events = hev ? kEvHost : kEvNone, o.hev = hev;
+  o.stamp = &e->pk_stamp, o.chunks = &e->pk_chunks;
+  return pk_run(e, h_blob, n, present, opts, o, h_rows_done);
+}
+
+extern "C" int cc_apply_batch_host_packed_results(cc_engine* e, const void* h_blob, uint64_t bytes, void* h_res_blob,
+                                                  uint64_t res_cap, uint64_t* res_bytes, const cc_events* hev,
+                                                  const cc_packed_opts* opts, uint64_t* h_rows_done) {
+  if (h_rows_done) *h_rows_done = 0;
+  if (!e) return set_err(CC_ERR_INVALID, "result blob: null argument");
+  TRY(res_blob_ok(h_res_blob, res_bytes));
+  if (opts && (opts->flags & ~(uint32_t)CC_PACKED_TIMELINE)) return set_err(CC_ERR_INVALID, "packed apply: unknown flag");
+  uint64_t n = 0;
+  uint32_t present = 0;
+  TRY(cc_pack_check(h_blob, bytes, &n, &present));  // (before anything is copied or launched)
+  TRY(host_events_ok(hev));
+  TRY(res_blob_room(n, res_cap, res_bytes));
+  if (n && (present & kPkNeed) != kPkNeed)
+    return set_err(CC_ERR_INVALID, "inst/op/flags/a/b columns and status/value outputs are required");
+  // from here on every return leaves a valid blob of the rows copied out so far
+  blob_header(kResultBlob, h_res_blob, 0, sizeof(cc_pack_header));
+  *res_bytes = sizeof(cc_pack_header);
+  HIPCHECK(hipSetDevice(e->device));
+  e->rp_chunks = 0;
+  if (n == 0) {
+    if (hev) *hev->count = 0;
+    return CC_OK;
+  }
+  PkSink o{};
+  o.results = kResBlob, o.res = (uint8_t*)h_res_blob, o.res_bytes = res_bytes;
+  o.events = hev ? kEvHost : kEvNone, o.hev = hev;
+  o.stamp = &e->rp_stamp, o.chunks = &e->rp_chunks;
+  return pk_run(e, h_blob, n, present, opts, o, h_rows_done);
+}
+
+extern "C" int cc_apply_batch_host_packed_events(cc_engine* e, const void* h_blob, uint64_t bytes, void* h_res_blob,
+                                                 uint64_t res_cap, uint64_t* res_bytes, void* h_ev_blob,
+                                                 uint64_t ev_capacity, uint64_t ev_cap_bytes, uint64_t* ev_bytes,
+                                                 uint64_t* ev_count, const cc_packed_opts* opts, uint64_t* h_rows_done) {
+  if (h_rows_done) *h_rows_done = 0;
+  if (!e) return set_err(CC_ERR_INVALID, "result blob: null argument");
+  TRY(res_blob_ok(h_res_blob, res_bytes));
+  if (!h_ev_blob || !ev_bytes || !ev_count) return set_err(CC_ERR_INVALID, "event blob: null argument");
+  if ((uintptr_t)h_ev_blob & 15) return set_err(CC_ERR_INVALID, "event blob: the blob must be 16-byte aligned");
+  if (opts && (opts->flags & ~(uint32_t)CC_PACKED_TIMELINE)) return set_err(CC_ERR_INVALID, "packed apply: unknown flag");
+  uint64_t n = 0;
+  uint32_t present = 0;
+  TRY(cc_pack_check(h_blob, bytes, &n, &present));  // (before anything is copied or launched)
+  TRY(res_blob_room(n, res_cap, res_bytes));
+  uint64_t bound = 0;
+  TRY(cc_evpack_bound(ev_capacity, &bound));
+  if (ev_cap_bytes < bound) {
+    *ev_bytes = bound;
+    return set_err(CC_ERR_CAPACITY, "event blob: the blob buffer is smaller than cc_evpack_bound (*ev_bytes = the bound)");
+  }
+  if (n && (present & kPkNeed) != kPkNeed)
+    return set_err(CC_ERR_INVALID, "inst/op/flags/a/b columns and status/value outputs are required");
+  // from here on every return leaves a valid result blob of the rows copied out so far and a valid event blob
+  blob_header(kResultBlob, h_res_blob, 0, sizeof(cc_pack_header));
+  *res_bytes = sizeof(cc_pack_header);
+  blob_header(kEventBlob, h_ev_blob, 0, sizeof(cc_pack_header));
+  *ev_bytes = sizeof(cc_pack_header);
+  *ev_count = 0;
+  HIPCHECK(hipSetDevice(e->device));
+  e->ep_chunks = 0;
+  if (n == 0) return CC_OK;
+  PkSink o{};
+  o.results = kResBlob, o.res = (uint8_t*)h_res_blob, o.res_bytes = res_bytes;
+  o.events = kEvDevice, o.ev_blob = h_ev_blob, o.ev_capacity = ev_capacity, o.ev_bytes = ev_bytes, o.ev_count = ev_count;
+  o.stamp = &e->ep_stamp, o.chunks = &e->ep_chunks;
+  return pk_run(e, h_blob, n, present, opts, o, h_rows_done);
+}
+
+extern "C" int cc_packed_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms) {
+  if (!e || !chunks || (cap && !h_ms)) return set_err(CC_ERR_INVALID, "null argument");
+  HIPCHECK(hipSetDevice(e->device));
+  *chunks = e->pk_chunks;
+  for (uint64_t k = 0; k < std::min(cap, e->pk_chunks); ++k)
+    for (int j = 0; j < 4; ++j)
+      HIPCHECK(hipEventElapsedTime(h_ms + 4 * k + j, e->pk_stamp[8 * k + 2 * j], e->pk_stamp[8 * k + 2 * j + 1]));
+  return CC_OK;
+}
+
+extern "C" int cc_packed_results_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms) {
+  if (!e || !chunks || (cap && !h_ms)) return set_err(CC_ERR_INVALID, "null argument");
+  HIPCHECK(hipSetDevice(e->device));
+  *chunks = e->rp_chunks;
+  for (uint64_t k = 0; k < std::min(cap, e->rp_chunks); ++k)
+    for (int j = 0; j < 5; ++j)
+      HIPCHECK(hipEventElapsedTime(h_ms + 5 * k + j, e->rp_stamp[10 * k + 2 * j], e->rp_stamp[10 * k + 2 * j + 1]));
+  return CC_OK;
 }
 
 extern "C" int cc_packed_events_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms) {
