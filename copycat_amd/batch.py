@@ -65,10 +65,24 @@ def _aligned_bytes(n, align=64):
     return buf[off:off + n]
 
 
+def pack_bound(n, columns=None):
+    """cc_pack_bound: the worst-case size of a blob of n rows with all nine columns, or with those named in `columns`."""
+    import ctypes as C
+
+    present = sum(1 << c for c, (name, _) in enumerate(abi.BATCH_COLUMNS) if columns is None or name in columns)
+    bound = C.c_uint64()
+    rc = _pack_lib().cc_pack_bound(n, present, C.byref(bound))
+    if rc:
+        _pack_fail(rc)
+    return bound.value
+
+
 def pack(b, columns=None, threads=0, out=None):
     """cc_pack_batch: the batch's columns (all nine, or those named in `columns`; the others are absent, the NULL
     column pointers of cc_batch) as one packed blob, a 16-byte-aligned uint8 array.  `out`: a 16-byte-aligned uint8
-    buffer to pack into (e.g. page-locked once and reused); the result is then a view of it."""
+    buffer to pack into (e.g. page-locked once and reused); the result is then a view of it.  Give it pack_bound()
+    bytes: into a smaller buffer the encoder first sizes the blob (it never writes into a buffer it refuses), one more
+    pass over the columns."""
     import ctypes as C
 
     L = _pack_lib()
@@ -84,11 +98,7 @@ def pack(b, columns=None, threads=0, out=None):
             present |= 1 << c
     blob = out
     if blob is None:
-        bound = C.c_uint64()
-        rc = L.cc_pack_bound(n, present, C.byref(bound))
-        if rc:
-            _pack_fail(rc)
-        blob = _aligned_bytes(bound.value)
+        blob = _aligned_bytes(pack_bound(n, columns))
     size = C.c_uint64()
     rc = L.cc_pack_batch(C.byref(s), n, blob.ctypes.data, blob.nbytes, threads, C.byref(size))
     if rc:

@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 
 ENGINE_SRCS = ["engine.hip", "apply_batch.hip", "map_big.hip", "partition.hip", "partition_ext.hip", "apply_value.hip", "value_path.hip", "apply_map.hip", "apply_map_hot.hip", "apply_coord.hip", "topic_fanout.hip", "events.hip", "quorum.hip", "close.hip", "map_wide.hip", "live.hip", "manager.hip", "retained.hip", "host_path.hip", "prefix_scan.hip", "map_small.hip", "map_cv.hip", "map_clear.hip", "wire.cpp", "split.cpp", "pack.cpp", "unpack.hip", "respack.cpp", "respack.hip", "evpack.cpp", "evpack.hip", "wire_gpu.hip"]
-ENGINE_HDRS = ["common.h", "engine_internal.h", "engine_state.h", "map_ops.h", "java_hashmap.h", "small_jhm.h", "jhm_tree.h", "big_jhm.h", "wire_plain.h"]
+ENGINE_HDRS = ["common.h", "engine_internal.h", "engine_state.h", "map_ops.h", "java_hashmap.h", "small_jhm.h", "jhm_tree.h", "big_jhm.h", "wire_plain.h", "pack_host.h", "pack_dev.h"]
 ENGINE_SO = os.path.join(HERE, "libcopycat_apply.so")
 WORKLOAD_SO = os.path.join(HERE, "libcopycat_workload.so")
 ARCH = os.environ.get("CC_OFFLOAD_ARCH", "gfx950")
@@ -32,38 +32,31 @@ def _run(cmd):
         raise RuntimeError(f"build failed: {' '.join(cmd)}")
 
 
-def build_engine(force=False):
-    deps = [os.path.join(CSRC, f) for f in ENGINE_SRCS + ENGINE_HDRS] + [os.path.join(ROOT, "include", "copycat_apply.h")]
-    if force or _stale(ENGINE_SO, deps):
-        hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-        flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall"]
-        objdir = os.path.join(HERE, "build_obj")
-        os.makedirs(objdir, exist_ok=True)
-        objs = [os.path.join(objdir, f + ".o") for f in ENGINE_SRCS]  # (respack.cpp and respack.hip, evpack.cpp and evpack.hip: the whole name)
-        # one hipcc per translation unit, in parallel (every kernel is launched from the unit that defines it)
-        from concurrent.futures import ThreadPoolExecutor
-
-        jobs = max(1, min(len(ENGINE_SRCS), int(os.environ.get("MAX_JOBS", os.cpu_count() or 1)), 16))
-        with ThreadPoolExecutor(jobs) as ex:
-            list(ex.map(lambda so: _run([hipcc, *flags, "-c", so[0], "-o", so[1]]), zip(ENGINE_SRCS, objs)))
-        _run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", ENGINE_SO])
-    return ENGINE_SO
-
-
-def build_variant(out_path, defines, tag):
-    """A diagnostics / A-B build of the engine with extra -D flags (object files under build_obj/<tag>)."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall"] + [f"-D{d}" for d in defines]
-    objdir = os.path.join(HERE, "build_obj", tag)
-    os.makedirs(objdir, exist_ok=True)
-    objs = [os.path.join(objdir, f + ".o") for f in ENGINE_SRCS]
+def _compile_engine(out_path, objdir, defines=()):
+    """One hipcc per translation unit, in parallel (every kernel is launched from the unit that defines it), then the link."""
     from concurrent.futures import ThreadPoolExecutor
 
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall"] + [f"-D{d}" for d in defines]
+    os.makedirs(objdir, exist_ok=True)
+    objs = [os.path.join(objdir, f + ".o") for f in ENGINE_SRCS]  # (respack.cpp and respack.hip, evpack.cpp and evpack.hip: the whole name)
     jobs = max(1, min(len(ENGINE_SRCS), int(os.environ.get("MAX_JOBS", os.cpu_count() or 1)), 16))
     with ThreadPoolExecutor(jobs) as ex:
         list(ex.map(lambda so: _run([hipcc, *flags, "-c", so[0], "-o", so[1]]), zip(ENGINE_SRCS, objs)))
     _run([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", out_path])
     return out_path
+
+
+def build_engine(force=False):
+    deps = [os.path.join(CSRC, f) for f in ENGINE_SRCS + ENGINE_HDRS] + [os.path.join(ROOT, "include", "copycat_apply.h")]
+    if force or _stale(ENGINE_SO, deps):
+        _compile_engine(ENGINE_SO, os.path.join(HERE, "build_obj"))
+    return ENGINE_SO
+
+
+def build_variant(out_path, defines, tag):
+    """A diagnostics / A-B build of the engine with extra -D flags (object files under build_obj/<tag>)."""
+    return _compile_engine(out_path, os.path.join(HERE, "build_obj", tag), defines)
 
 
 def build_workload(force=False):

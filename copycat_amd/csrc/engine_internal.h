@@ -762,7 +762,7 @@ struct RespackArgs {
   uint64_t data_base;
   unsigned long long* total;
 };
-constexpr uint32_t kRespackPlacePass = 256;  // blocks one pass of the placement scan holds (one per lane)
+constexpr uint32_t kPackPlacePass = 256;  // blocks one pass of an encoder's placement scan holds (one per lane)
 int launch_respack(const RespackArgs& a, hipStream_t st);
 
 // Wide event columns -> the directory and data areas of an event blob (evpack.hip): block k of `dir` encodes events

@@ -2,8 +2,8 @@
 //
 // k_unpack: one workgroup of 256 lanes per block of CC_PACK_BLOCK_ROWS rows.  The block's directory entry is the same
 // for every lane (read through readfirstlane: the branches on mode and width are scalar branches).  Per column:
-//   1. the packed rows (at most 32 KiB) go global -> LDS with 16-byte loads, lane i the i-th 16 bytes: each wave
-//      instruction reads one contiguous KiB, whatever the width;
+//   1. the packed rows (at most 32 KiB) go global -> LDS with 16-byte loads, lane i the i-th 16 bytes (pack_dev.h
+//      stage): each wave instruction reads one contiguous KiB, whatever the width;
 //   2. each lane reads the narrow offsets of the rows it owns from LDS, widens them and writes ONE 16-byte store:
 //      two u64 rows, four u32 rows or sixteen u8 rows per lane, so a wave store is one contiguous KiB (narrow stores
 //      cost several times a 16-byte store per byte).
@@ -12,19 +12,13 @@
 // the a rows it has just written itself (a and b share the row -> lane mapping), so no fence is needed.
 // The kernel moves (packed + wide) bytes once; its bar is the H2D of the same chunk, an order of magnitude slower.
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): no scratch, 32 KiB LDS.
-#include <hip/hip_runtime.h>
-
-#include "engine_state.h"
+#include "pack_dev.h"
 
 namespace cc {
 
 namespace {
 
-constexpr uint32_t kRows = CC_PACK_BLOCK_ROWS;
-constexpr uint32_t kLanes = 256;
-
-__device__ inline uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ inline uint64_t uni(uint64_t v) { return (uint64_t)uni((uint32_t)v) | ((uint64_t)uni((uint32_t)(v >> 32)) << 32); }
+using namespace pkd;
 
 struct Col {  // one directory entry, wave-uniform
   uint32_t mode, width, offset;
@@ -32,13 +26,6 @@ struct Col {  // one directory entry, wave-uniform
 };
 __device__ inline Col col_of(const cc_pack_col& e) {
   return Col{uni((uint32_t)e.mode), uni((uint32_t)e.width), uni(e.offset), uni(e.base)};
-}
-
-// `bytes` (a multiple of 16) of packed rows into LDS; the barrier before it frees the image of the previous column
-__device__ inline void stage(uint8_t* lds, const uint8_t* src, uint32_t bytes) {
-  __syncthreads();
-  for (uint32_t i = threadIdx.x * 16; i < bytes; i += kLanes * 16) *(uint4*)(lds + i) = *(const uint4*)(src + i);
-  __syncthreads();
 }
 
 template <int W>
@@ -80,7 +67,7 @@ __device__ inline void dec64(const uint8_t* lds, uint64_t* out, const uint64_t* 
 __device__ inline void unpack64(const cc_pack_col& e, const uint8_t* area, uint8_t* lds, uint64_t* out, const uint64_t* a,
                                 uint32_t rows) {
   const Col c = col_of(e);
-  if (c.width) stage(lds, area + c.offset, (rows * c.width + 15) & ~15u);
+  if (c.width) stage(lds, area + c.offset, r16(rows * c.width));
   if (c.mode == CC_PK_REL_A) {
     if (c.width == 1) dec64<1, true>(lds, out, a, 0, rows);
     else if (c.width == 2) dec64<2, true>(lds, out, a, 0, rows);
@@ -111,7 +98,7 @@ __device__ inline void dec32(const uint8_t* lds, uint32_t* out, uint32_t base, u
 
 __device__ inline void unpack32(const cc_pack_col& e, const uint8_t* area, uint8_t* lds, uint32_t* out, uint32_t rows) {
   const Col c = col_of(e);
-  if (c.width) stage(lds, area + c.offset, (rows * c.width + 15) & ~15u);
+  if (c.width) stage(lds, area + c.offset, r16(rows * c.width));
   const uint32_t base = (uint32_t)c.base;
   if (c.width == 0) dec32<0>(lds, out, base, rows);
   else if (c.width == 1) dec32<1>(lds, out, base, rows);
@@ -125,7 +112,7 @@ __device__ inline uint32_t add_bytes(uint32_t x, uint32_t b) {
 }
 __device__ inline void unpack8(const cc_pack_col& e, const uint8_t* area, uint8_t* lds, uint8_t* out, uint32_t rows) {
   const Col c = col_of(e);
-  if (c.width) stage(lds, area + c.offset, (rows + 15) & ~15u);
+  if (c.width) stage(lds, area + c.offset, r16(rows));
   const uint32_t b4 = ((uint32_t)c.base & 0xFFu) * 0x01010101u;
   const uint32_t r = threadIdx.x * 16;
   if (r >= rows) return;

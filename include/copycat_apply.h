@@ -754,8 +754,9 @@ typedef struct cc_pack_block {
 
 /* Host side, no GPU involved.  cc_pack_bound: the worst-case blob size of n rows with the `present` columns.
  * cc_pack_batch: h_cols (NULL column = absent) -> h_blob (16-byte aligned, cap bytes); *bytes = the blob's size; a cap
- * too small returns CC_ERR_CAPACITY with *bytes = the size needed and writes nothing.  One block at a time per thread
- * (the block stays in cache between the min / max pass and the narrow write); threads = 0: hardware concurrency.
+ * too small returns CC_ERR_CAPACITY with *bytes = the size needed and writes nothing (so a cap below cc_pack_bound is
+ * sized first, one more min / max pass over the columns: pass the bound).  One block at a time per thread (the block
+ * stays in cache between the min / max pass and the narrow write); threads = 0: hardware concurrency.
  * cc_pack_check: the single validator every consumer runs first: magic, version, sizes, the directory inside the blob,
  * every block's rows (their sum = n), every offset aligned, inside its area and non-overlapping, mode and width legal
  * for the column, REL_A only on b and only with a.  Any violation is CC_ERR_INVALID (message: cc_last_error); a blob

@@ -50,7 +50,7 @@ def worker(args):
     import torch  # noqa: F401
 
     from copycat_amd import abi
-    from copycat_amd.batch import Batch, _aligned_bytes, pack, results_bound
+    from copycat_amd.batch import Batch, _aligned_bytes, pack, pack_bound, results_bound
     from copycat_amd.engine import Engine, _check, host_register
 
     w = args.workload
@@ -115,7 +115,7 @@ def worker(args):
         step = int(line)
         b = batch(step)
         if blob_buf is None:
-            blob_buf = _aligned_bytes(len(pack(b)) + (64 << 20))
+            blob_buf = _aligned_bytes(pack_bound(n))
             host_register(blob_buf)
         blob = pack(b, threads=16, out=blob_buf)
         out = {"step": step}

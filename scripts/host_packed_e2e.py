@@ -32,7 +32,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from copycat_amd import abi  # noqa: E402
-from copycat_amd.batch import Batch, _aligned_bytes, pack, pack_info, results_bound, results_check  # noqa: E402
+from copycat_amd.batch import Batch, _aligned_bytes, pack, pack_bound, pack_info, results_bound, results_check  # noqa: E402
 from copycat_amd.engine import RESULT_SENTINEL, Engine, _check, host_register, host_unregister  # noqa: E402
 from copycat_amd.workload import SEED_C2, AtomicLongClients  # noqa: E402
 
@@ -78,7 +78,7 @@ def main():
     clients = AtomicLongClients(resources=R, seed=SEED_C2, threads=args.threads)
     EW, EP, EB = _engine(n), _engine(n), _engine(n)
     host = Batch(n)
-    blob_buf = _aligned_bytes(14 * n + (1 << 20))  # (12 B per row is the workload's pinned ceiling: tests/test_pack.py)
+    blob_buf = _aligned_bytes(pack_bound(n, COLS))  # (below the bound cc_pack_batch sizes the blob first: a second pass)
     res = [(np.full(n, RESULT_SENTINEL, np.uint8), np.zeros(n, np.uint64)) for _ in range(2)]
     res_buf = _aligned_bytes(results_bound(n))
     ds, dv = np.zeros(n, np.uint8), np.zeros(n, np.uint64)  # the result blob decoded on the host

@@ -101,6 +101,14 @@ Blob pack_random(uint64_t n, uint32_t present, uint32_t threads) {
   if (cc_pack_batch(&in, n, nullptr, 0, threads, &need) != CC_ERR_CAPACITY) die("a zero capacity was not refused");
   if (need > bound) die("the blob is larger than cc_pack_bound");
   Blob b{(uint8_t*)exact(need), need};
+  if (need > 64) {  // one byte short: refused, and not a byte written (an exact-size buffer: a write is a report)
+    Blob s{(uint8_t*)exact(need - 1), need - 1};
+    std::memset(s.p, 0xEE, (size_t)s.bytes);
+    if (cc_pack_batch(&in, n, s.p, s.bytes, threads, &got) != CC_ERR_CAPACITY || got != need) die("a short capacity was not refused");
+    for (uint64_t i = 0; i < s.bytes; ++i)
+      if (s.p[i] != 0xEE) die("a refused encode wrote into the buffer");
+    std::free(s.p);
+  }
   if (cc_pack_batch(&in, n, b.p, need, threads, &got) != CC_OK || got != need) die("cc_pack_batch failed at the exact size");
   uint64_t n2 = ~0ull;
   uint32_t p2 = ~0u;

@@ -16,6 +16,7 @@ from copycat_amd.batch import (Batch, _aligned_bytes, events_bound, events_check
 from tests import evpack_cases as ec
 from tests import pack_cases as pc
 from tests.test_gpu_pack import COORD_K, COORD_TYPES, EV_KEYS, _coord_engine, _coord_stream, _state
+from tests.test_gpu_respack import _place_pass
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +24,7 @@ B = pc.B
 CHUNK = 2 * B         # chunk_rows of the overflow test (test_gpu_respack.py's)
 N = 2 * CHUNK + 3616  # 20,000 rows: three chunks, the last one ragged
 NT = 3 * B + 1        # 12,289 rows in 4,096-row chunks: chunk boundaries fall inside event blocks
-PLACE_PASS = 256      # blocks one pass of k_evpack_place holds (one per lane)
+PLACE_PASS = _place_pass()  # blocks one pass of k_evpack_place holds (one per lane)
 
 
 @pytest.fixture(scope="module")

@@ -28,9 +28,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _place_pass():
-    """kRespackPlacePass: the blocks one pass of the placement scan (k_respack_place) holds."""
+    """kPackPlacePass: the blocks one pass of an encoder's placement scan (k_respack_place, k_evpack_place) holds."""
     txt = open(os.path.join(ROOT, "copycat_amd", "csrc", "engine_internal.h")).read()
-    return int(re.search(r"kRespackPlacePass\s*=\s*(\d+)", txt).group(1))
+    return int(re.search(r"kPackPlacePass\s*=\s*(\d+)", txt).group(1))
 
 
 @pytest.fixture(scope="module")
@@ -46,6 +46,10 @@ def _encode_cases():
     out = [(f"random/{n}", *rc.random_results(n, seed=n)) for n in (1, 15, 16, 17, B - 1, B, B + 1, 3 * B + 5)]
     status, value, _ = rc.width_rows()
     out.append(("widths", status, value))
+    # raw values (width 8) with mixed status: a full block, and a tail block of 3 rows or of 1,003 (an odd length)
+    for n in (B + 3, B + 1003):
+        value = np.resize(np.array([0, rc.M64, 1 << 63, 5], np.uint64), n)
+        out.append((f"raw/{n}", (np.arange(n) % 3 * 0x10).astype(np.uint8), value))
     # one block more than a pass of the placement scan: constant blocks (no data) but a few, spread over both passes
     blocks = _place_pass() + 1
     status, value = np.full(blocks * B, 0x10, np.uint8), np.full(blocks * B, 3, np.uint64)
