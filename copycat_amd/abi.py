@@ -277,6 +277,15 @@ class cc_wire_stats(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("rows", "device_rows", "host_rows")]
 
 
+# the device String dictionary (include/copycat_apply.h "the device String dictionary")
+CC_WIRE_STR_MAX = 256
+
+
+class cc_wire_dict_info(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("strings", "long_strings", "pool_bytes", "cells", "full_uploads",
+                                                "last_sync_strings", "last_str_rows")]
+
+
 # packed host batches (include/copycat_apply.h "packed host batches"; copycat_amd/csrc/pack.cpp, unpack.hip)
 CC_PACK_BLOCK_ROWS = 4096
 CC_PACK_VERSION = 1

@@ -111,6 +111,7 @@ static void free_all(cc_engine* e) {
     if (p) (void)hipFree(p), p = nullptr;
   for (void*& p : e->wr_buf)
     if (p) (void)hipFree(p), p = nullptr;
+  (void)cc_wire_dict_detach(e);
   if (e->wr_pin) (void)hipHostFree(e->wr_pin);
   for (hipEvent_t ev : e->wr_ev)
     if (ev) (void)hipEventDestroy(ev);
@@ -781,6 +782,7 @@ extern "C" int cc_handle_hashes(cc_engine* e, const uint64_t* h_handles, const i
   if (count == 0) return CC_OK;
   int rc = quiesce(e);
   if (rc) return rc;
+  ++e->hh_gen;
   for (uint64_t i = 0; i < count; ++i) {
     auto it = e->hh.find(h_handles[i]);
     if (it != e->hh.end() && it->second != h_hashes[i])
@@ -1869,6 +1871,7 @@ extern "C" int cc_snapshot_restore(cc_engine* e, const void* h_buf, uint64_t siz
       hv[i] = (int32_t)(uint32_t)t[1];
     }
     e->hh.clear();
+    ++e->hh_gen;
     if (nh && (rc = cc_handle_hashes(e, hk.data(), hv.data(), nh))) return rc;
   }
   HIPCHECK(hipMemset(e->d_err, 0, sizeof(uint32_t)));

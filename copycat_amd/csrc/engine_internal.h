@@ -2,7 +2,11 @@
 #pragma once
 #include <cstdlib>
 
+#include <map>
+#include <vector>
+
 #include "common.h"
+#include "wire_plain.h"
 
 // A/B and diagnostics switches read from the environment (CC_NO_HOT, CC_EV_V1, CC_EV_SCATTER, CC_PART_EXT_1024) exist
 // only in -DCC_DIAG builds (copycat_amd/build.py build_variant); the product library never takes an untested path.
@@ -806,7 +810,9 @@ struct WireArgs {
   uint64_t* aux;
   uint64_t* iid;             // may be null
   uint64_t* esc;             // [ceil(n / 64)]
-  unsigned long long* esc_n; // escaped rows (zeroed by the caller)
+  unsigned long long* esc_n; // escaped rows (zeroed by the caller); with a dictionary esc_n[1] counts the decoded
+                             // rows that carry a resolved String
+  DictView dict;             // the device String dictionary (cells == null: none, the plain kernel runs)
 };
 int launch_wire_decode(const WireArgs& a, hipStream_t st);
 // one host-decoded row written over the device columns (k_wire_patch)
@@ -823,6 +829,40 @@ inline uint32_t wire_tbl_hash(uint64_t id, uint32_t mask) { return (uint32_t)((i
 int wire_decode_one(cc_engine* e, const cc_wire_codec& c, cc_wire_interner* in, const uint8_t* p, const uint8_t* end,
                     uint64_t row, uint64_t at, const cc_wire_out* out);
 int wire_register_keys(cc_engine* e, cc_wire_interner* in, const uint64_t* keys, uint64_t m);
+// wire.cpp: the host mirror of the String dictionary (wire_plain.h): the exact image of the table and the pool; the
+// device holds a copy of it (wire_gpu.hip).  Plain C++, no HIP call.
+struct WireDict {
+  std::vector<DictCell> cells;    // a power of two, at least twice `strings`
+  std::vector<uint64_t> pool;     // every String 8-byte aligned, zero-padded to whole words
+  std::vector<uint32_t> cell_of;  // interner rank -> cell (~0u: left out, longer than CC_WIRE_STR_MAX)
+  std::vector<uint32_t> dirty;    // cells changed since the device last took them (not kept across a rebuild)
+  uint64_t strings = 0, long_strings = 0;
+  uint64_t pool_sent = 0;         // pool words the device holds
+  bool rebuilt = true;            // the table was rebuilt (doubled): the device needs all of it
+  DictView view(uint64_t first) const { return DictView{cells.data(), pool.data(), (uint32_t)(cells.size() - 1), first}; }
+};
+struct WireInternerInfo {
+  uint64_t serial, first, count;
+};
+WireInternerInfo wire_interner_info(const cc_wire_interner* in);
+// Add the interner's Strings from rank d.cell_of.size() on; -> Strings added to the table.  `hh`: the handles whose
+// String.hashCode is registered (a new cell's key bit); remark: recompute every cell's key bit from it.
+uint64_t wire_dict_sync(WireDict& d, const cc_wire_interner* in, const std::map<uint64_t, int32_t>& hh, bool remark);
+// set the key bit of the cells of these handles (those the dictionary holds)
+void wire_dict_mark_keys(WireDict& d, uint64_t first, const uint64_t* handles, uint64_t m);
+// the device side of an attachment (wire_gpu.hip)
+struct WireDictDev {
+  WireDict host;
+  const cc_wire_interner* in = nullptr;  // identity only: compared, never followed
+  uint64_t serial = 0, first = 0;
+  uint64_t hh_gen = 0;                   // e->hh_gen the key bits are current with
+  void* d_cells = nullptr;
+  void* d_pool = nullptr;
+  void* d_list = nullptr;                // staged (cell index, cell) pairs for k_dict_scatter
+  size_t cells_cap = 0, pool_cap = 0, list_cap = 0;  // cells / words / pairs
+  uint64_t full_uploads = 0, last_sync_strings = 0, last_str_rows = 0;
+};
+
 // The decode behind cc_wire_decode_to_device and cc_apply_wire_host (wire_gpu.hip).  stop_at_ctl: the fallback stops
 // at the first manager entry (row *stop_row, else n): rows after it are neither interned nor checked.
 int wire_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* in, const uint8_t* h_buf, uint64_t buf_len,

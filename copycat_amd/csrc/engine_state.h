@@ -440,6 +440,10 @@ struct cc_engine {
   uint64_t* wr_pin = nullptr;  // pinned: the escape count
   hipEvent_t wr_ev[4] = {};    // the last decode's stages (cc_wire_timeline): before the H2D, the kernel, the escape
   bool wr_timed = false;       // read-back, and after it
+  // The device String dictionary of the wire decoder (cc_wire_dict_attach; wire_gpu.hip): null when none is attached.
+  // hh_gen moves whenever hh changes (cc_handle_hashes, snapshot restore): the dictionary re-marks its key bits then.
+  cc::WireDictDev* wdict = nullptr;
+  uint64_t hh_gen = 1;
   // per-kernel profiling (cc_profile_enable)
   bool prof_on = false;
   std::vector<hipEvent_t> ev_pool;

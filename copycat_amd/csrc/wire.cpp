@@ -12,6 +12,7 @@
 // byte before a registered type id, the ids of the boxed primitives and String, byte order, writeUTF8's
 // framing — are parameters (cc_wire_codec) whose defaults restate Catalyst 1.x as documented in DESIGN.md; the
 // byte layout is "parity unpinned", the field order per op is pinned to the reference's writeObject sources.
+#include <atomic>
 #include <cstring>
 #include <string>
 #include <unordered_map>
@@ -84,6 +85,11 @@ struct cc_wire_interner {
   std::vector<std::string> strs;  // handle - first -> bytes
   uint64_t first;
   std::vector<int32_t> hashes;    // handle - first -> java.lang.String.hashCode
+  uint64_t serial = next_serial();  // process-unique: tells an interner from one re-created at its address
+  static uint64_t next_serial() {
+    static std::atomic<uint64_t> n{0};
+    return ++n;
+  }
 };
 
 using namespace cc;
@@ -303,6 +309,74 @@ int cc::wire_register_keys(cc_engine* e, cc_wire_interner* in, const uint64_t* k
       hv.push_back(in->hashes[keys[i] - in->first]);
     }
   return hk.empty() ? CC_OK : cc_handle_hashes(e, hk.data(), hv.data(), hk.size());
+}
+
+// ---- the host mirror of the device String dictionary (engine_internal.h WireDict; the layout: wire_plain.h) ----
+cc::WireInternerInfo cc::wire_interner_info(const cc_wire_interner* in) {
+  return WireInternerInfo{in->serial, in->first, (uint64_t)in->strs.size()};
+}
+
+namespace {
+
+// the String of `rank` into the table: its bytes are at pool word `off8` already
+void dict_place(WireDict& d, uint32_t rank, uint32_t len, uint64_t off8, uint64_t hash, uint32_t flags) {
+  const uint32_t mask = (uint32_t)(d.cells.size() - 1);
+  uint32_t at = (uint32_t)hash & mask;
+  while (d.cells[at].flags & kDictUsed) at = (at + 1) & mask;
+  DictCell& c = d.cells[at];
+  c.hash = hash, c.len = len, c.flags = kDictUsed | flags, c.off = off8 * 8, c.rank = rank, c.pad = 0;
+  d.cell_of[rank] = at;
+  if (!d.rebuilt) d.dirty.push_back(at);
+}
+
+}  // namespace
+
+uint64_t cc::wire_dict_sync(WireDict& d, const cc_wire_interner* in, const std::map<uint64_t, int32_t>& hh, bool remark) {
+  if (d.cells.empty()) d.cells.assign(64, DictCell{}), d.rebuilt = true;
+  const uint64_t before = d.strings;
+  for (uint64_t rank = d.cell_of.size(); rank < in->strs.size(); ++rank) {
+    const std::string& s = in->strs[rank];
+    d.cell_of.push_back(~0u);
+    if (s.size() > CC_WIRE_STR_MAX || rank > 0xFFFFFFFEull) {  // (a cell's rank is 32 bits: Strings past it are left out too)
+      ++d.long_strings;
+      continue;
+    }
+    if (2 * (d.strings + 1) > d.cells.size()) {  // doubling: every cell moves (the pool stays)
+      std::vector<DictCell> old = std::move(d.cells);
+      d.cells.assign(2 * old.size(), DictCell{});
+      d.rebuilt = true;
+      d.dirty.clear();
+      for (const DictCell& c : old)
+        if (c.flags & kDictUsed) dict_place(d, c.rank, c.len, c.off / 8, c.hash, c.flags & ~kDictUsed);
+    }
+    const uint64_t off8 = d.pool.size();
+    d.pool.resize(off8 + (s.size() + 7) / 8, 0);
+    if (!s.empty()) memcpy(d.pool.data() + off8, s.data(), s.size());
+    const uint64_t h = dict_hash(HostBytes{(const uint8_t*)s.data()}, 0, (uint32_t)s.size());
+    dict_place(d, (uint32_t)rank, (uint32_t)s.size(), off8, h, hh.count(in->first + rank) ? kDictKeyReg : 0u);
+    ++d.strings;
+  }
+  if (remark)
+    for (uint64_t rank = 0; rank < d.cell_of.size(); ++rank) {
+      const uint32_t at = d.cell_of[rank];
+      if (at == ~0u) continue;
+      const uint32_t want = kDictUsed | (hh.count(in->first + rank) ? kDictKeyReg : 0u);
+      if (d.cells[at].flags != want) {
+        d.cells[at].flags = want;
+        if (!d.rebuilt) d.dirty.push_back(at);
+      }
+    }
+  return d.strings - before;
+}
+
+void cc::wire_dict_mark_keys(WireDict& d, uint64_t first, const uint64_t* handles, uint64_t m) {
+  for (uint64_t i = 0; i < m; ++i) {
+    if (handles[i] < first || handles[i] - first >= d.cell_of.size()) continue;
+    const uint32_t at = d.cell_of[handles[i] - first];
+    if (at == ~0u || (d.cells[at].flags & kDictKeyReg)) continue;
+    d.cells[at].flags |= kDictKeyReg;
+    if (!d.rebuilt) d.dirty.push_back(at);
+  }
 }
 
 extern "C" void cc_wire_codec_default(cc_wire_codec* c) {

@@ -25,8 +25,27 @@
 // The kernel moves (entry bytes + 8 B offset + 38 B columns) per row once; its bar is the H2D of its own input.
 // Measured (scripts/wire_rate.py, profiles/wire_gpu/rate.json: 16 Mi CompareAndSet entries of 34 bytes, MI355X): the
 // kernel takes 0.77 ms (1.7 TB/s over those bytes), the H2D of the same input 12.5 ms.
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): k_wire_decode 95 VGPRs, 106 SGPRs (252 SGPR spills,
-// to VGPR lanes), no scratch, 29,504 B LDS, occupancy 5 waves / SIMD; k_wire_patch 30 VGPRs, no scratch, no LDS.
+//
+// The String dictionary (cc_wire_dict_attach; layout, hash and probe: wire_plain.h).  k_wire_decode is a template:
+// <false> is the kernel above, unchanged, and the only one an engine without a dictionary (or a call with another
+// interner) launches; <true> runs the same parser over a DictView, so a String of at most CC_WIRE_STR_MAX bytes that
+// the attached interner holds becomes a HANDLE in the lane that parses the entry: the lane hashes the bytes from its
+// LDS window 8 at a time (LdsBytes::le64, the tail masked), reads the cell (32 bytes, one cache line) and compares the
+// pool's words with the window's; two dependent global reads per String, hidden by the other waves of the SIMD.  The
+// threshold of step 1 becomes kWireStrEntryMax (836 bytes: MAP_REPLACEIFPRESENT with three Strings), which fits a
+// window twenty times over, so a window still holds any 256 consecutive plain entries and still parses its first
+// entry.  An unknown or longer String, and a String key whose hash is not registered, escape as in step 5.  The host
+// keeps the exact image (wire.cpp WireDict); wire_dict_update sends what changed before the decode: the pool's new
+// words, and the changed cells as a list that k_dict_scatter writes, or the whole table after a doubling.
+// Measured (scripts/wire_rate.py --strings, profiles/wire_gpu/rate_strings.json: 16 Mi Put entries of 53 bytes with a
+// 16-byte String key, MI355X): with 1,024 keys (table and pool in L2) the
+// kernel takes 1.67 ms, with 1 Mi keys (64 MiB table + 16 MiB pool: the Infinity Cache) 2.21 ms, the H2D of the
+// same input 18.5 ms; the call takes 195 / 206 ms where the same engine unattached (every row escapes) takes
+// 2298 / 14034 ms.  On an all-plain stream <true> is 7.1 % slower than <false> (rate_plain_ab.json: its occupancy).
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): k_wire_decode<false> 95 VGPRs, 106 SGPRs (174 SGPR
+// spills, to VGPR lanes), no scratch, 29,504 B LDS, occupancy 5 waves / SIMD; k_wire_decode<true> 100 VGPRs, 106 SGPRs
+// (197 SGPR spills, to VGPR lanes), no scratch, 29,504 B LDS, occupancy 4 waves / SIMD; k_wire_patch 30 VGPRs,
+// k_dict_scatter 10 VGPRs, both no scratch, no LDS.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -64,6 +83,9 @@ struct LdsBytes {
     return (uint64_t)__builtin_amdgcn_alignbyte(w1, w0, at & 3u) |
            ((uint64_t)__builtin_amdgcn_alignbyte(w2, w1, at & 3u) << 32);
   }
+  // bytes [i, i + n), n in 1..7: the same three dwords (they lie inside the LDS array wherever the entry ends),
+  // the bytes past n masked off
+  __device__ uint64_t lepart(uint32_t i, uint32_t n) const { return le64(i) & (~0ull >> (64 - 8 * n)); }
 };
 
 __device__ inline uint32_t slot_of(const WireArgs& a, uint64_t id) {
@@ -90,6 +112,10 @@ __device__ inline void store_col(T* out, const T* lds, uint32_t rows) {
   }
 }
 
+// the longest entry the parser with a dictionary yields fits a window by itself, so every window parses its first entry
+static_assert(15 + kWireStrEntryMax <= kWin, "the longest device-parsable entry fits one window");
+
+template <bool kDict>
 __global__ __launch_bounds__(256) void k_wire_decode(WireArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t win[kWin + 16];
   __shared__ __attribute__((aligned(16))) uint64_t o64[5][kWireLanes];  // key, a, b, aux, iid
@@ -102,6 +128,7 @@ __global__ __launch_bounds__(256) void k_wire_decode(WireArgs a) {
   static_assert(kSchemaIds == kWireLanes, "one schema word per lane");
   const uint64_t t0 = (uint64_t)blockIdx.x * kWireTile;
   const uint64_t base0 = a.off[0];
+  uint32_t str_rows = 0;  // (kDict) this wave's decoded rows with a resolved String, over the tile
   for (uint32_t g = 0; g < kWireTile / kWireLanes; ++g) {
     const uint64_t g0 = t0 + (uint64_t)g * kWireLanes;
     if (g0 >= a.n) break;  // (the same in every lane)
@@ -109,7 +136,8 @@ __global__ __launch_bounds__(256) void k_wire_decode(WireArgs a) {
     const bool valid = tid < rows;
     const uint64_t beg = valid ? a.off[g0 + tid] - base0 : 0, end = valid ? a.off[g0 + tid + 1] - base0 : 0;
     const uint64_t gend = a.off[g0 + rows] - base0;
-    bool pend = valid && end - beg <= kWirePlainMax;  // still to parse; the longer ones escape unread
+    // still to parse; the longer ones escape unread
+    bool pend = valid && end - beg <= (kDict ? kWireStrEntryMax : kWirePlainMax);
     bool plain = false;
     PlainRow r{};
     for (;;) {
@@ -125,7 +153,9 @@ __global__ __launch_bounds__(256) void k_wire_decode(WireArgs a) {
       __syncthreads();
       if (pend && end <= wbase + kWin) {
         pend = false;
-        plain = wire_plain_parse(LdsBytes{win, (uint32_t)(beg - wbase)}, (uint32_t)(end - beg), a.codec, s_sch, r);
+        const LdsBytes ent{win, (uint32_t)(beg - wbase)};
+        if constexpr (kDict) plain = wire_parse(ent, (uint32_t)(end - beg), a.codec, s_sch, a.dict, r);
+        else plain = wire_plain_parse(ent, (uint32_t)(end - beg), a.codec, s_sch, r);
       }
     }
     o64[0][tid] = plain ? r.key : 0;
@@ -141,6 +171,7 @@ __global__ __launch_bounds__(256) void k_wire_decode(WireArgs a) {
       a.esc[(g0 >> 6) + wave] = esc;
       if (esc) atomicAdd(a.esc_n, (unsigned long long)__popcll(esc));
     }
+    if constexpr (kDict) str_rows += (uint32_t)__popcll(__ballot(plain && r.strs != 0));
     __syncthreads();
     store_col(a.key + g0, o64[0], rows);
     store_col(a.a + g0, o64[1], rows);
@@ -151,6 +182,12 @@ __global__ __launch_bounds__(256) void k_wire_decode(WireArgs a) {
     store_col(a.op + g0, o8[0], rows);
     store_col(a.flags + g0, o8[1], rows);
     __syncthreads();  // (the next group writes the LDS columns again)
+  }
+  if constexpr (kDict) {  // one atomic per tile: every wave adding to the one counter serialises in L2
+    if (lane == 0) s_first[wave] = str_rows;
+    __syncthreads();
+    const uint64_t sum = s_first[0] + s_first[1] + s_first[2] + s_first[3];
+    if (tid == 0 && sum) atomicAdd(a.esc_n + 1, (unsigned long long)sum);
   }
 }
 
@@ -168,6 +205,20 @@ __global__ __launch_bounds__(256) void k_wire_patch(WireArgs a, const WirePatch*
   a.b[p.row] = p.b;
   a.aux[p.row] = p.aux;
   if (a.iid) a.iid[p.row] = p.iid;
+}
+
+// changed dictionary cells over the device table: one lane per (cell index, cell) pair
+struct DictPatch {
+  uint32_t at, pad[7];
+  DictCell cell;
+};
+static_assert(sizeof(DictPatch) == 64, "DictPatch");
+__global__ __launch_bounds__(256) void k_dict_scatter(DictCell* cells, uint32_t mask, const DictPatch* list, uint64_t m) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= m) return;
+  const uint32_t at = list[i].at;
+  if (at > mask) return;
+  cells[at] = list[i].cell;
 }
 
 enum WrSlot : int { kWrBytes = 0, kWrOff, kWrEsc, kWrTable, kWrSchema, kWrPatch };
@@ -214,13 +265,81 @@ int wire_table(cc_engine* e, hipStream_t st) {
   return CC_OK;
 }
 
+// a device buffer of the dictionary with room for `bytes`; keep: the first `keep` bytes survive a reallocation
+int dict_buf(void** buf, size_t* cap_bytes, size_t bytes, size_t keep, hipStream_t st) {
+  if (*cap_bytes >= bytes) return CC_OK;
+  const size_t cap = std::max<size_t>(std::max<size_t>(bytes, *cap_bytes * 2), 4096);
+  void* p = nullptr;
+  const hipError_t x = hipMalloc(&p, cap);
+  if (x != hipSuccess) return set_err(CC_ERR_HIP, "hipMalloc (wire dictionary)", x);
+  if (*buf && keep) {
+    if (hipMemcpyAsync(p, *buf, keep, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+      (void)hipFree(p);
+      return set_err(CC_ERR_HIP, "wire dictionary: pool copy");
+    }
+  }
+  if (*buf) (void)hipFree(*buf);
+  *buf = p;
+  *cap_bytes = cap;
+  return CC_OK;
+}
+
+// Bring the attached dictionary up to date with its interner and the engine's registered hashes, the host mirror
+// first, then the device copy: the new pool words, and either the changed cells (a list and k_dict_scatter) or,
+// after a doubling, the whole table.  Synchronous on `st` when anything moved.
+int wire_dict_update(cc_engine* e, const cc_wire_interner* in, hipStream_t st) {
+  WireDictDev& w = *e->wdict;
+  WireDict& d = w.host;
+  const bool grown = wire_interner_info(in).count != d.cell_of.size(), remark = w.hh_gen != e->hh_gen;
+  if (grown || remark) {
+    w.last_sync_strings = wire_dict_sync(d, in, e->hh, remark);
+    w.hh_gen = e->hh_gen;
+  }
+  if (!d.rebuilt && d.dirty.empty() && d.pool_sent == d.pool.size()) return CC_OK;
+  size_t cap = w.pool_cap * 8;
+  TRY(dict_buf(&w.d_pool, &cap, (d.pool.size() + 1) * 8, d.pool_sent * 8, st));
+  w.pool_cap = cap / 8;
+  if (d.pool.size() > d.pool_sent)
+    HIPCHECK(hipMemcpyAsync((uint64_t*)w.d_pool + d.pool_sent, d.pool.data() + d.pool_sent, (d.pool.size() - d.pool_sent) * 8,
+                            hipMemcpyHostToDevice, st));
+  std::vector<DictPatch> list;
+  if (d.rebuilt) {
+    cap = w.cells_cap * sizeof(DictCell);
+    TRY(dict_buf(&w.d_cells, &cap, d.cells.size() * sizeof(DictCell), 0, st));
+    w.cells_cap = cap / sizeof(DictCell);
+    HIPCHECK(hipMemcpyAsync(w.d_cells, d.cells.data(), d.cells.size() * sizeof(DictCell), hipMemcpyHostToDevice, st));
+    ++w.full_uploads;
+  } else if (!d.dirty.empty()) {
+    list.resize(d.dirty.size());
+    for (size_t i = 0; i < list.size(); ++i) list[i] = DictPatch{d.dirty[i], {}, d.cells[d.dirty[i]]};  // (a cell listed twice carries the same image twice)
+    cap = w.list_cap * sizeof(DictPatch);
+    TRY(dict_buf(&w.d_list, &cap, list.size() * sizeof(DictPatch), 0, st));
+    w.list_cap = cap / sizeof(DictPatch);
+    HIPCHECK(hipMemcpyAsync(w.d_list, list.data(), list.size() * sizeof(DictPatch), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_dict_scatter, dim3((uint32_t)((list.size() + 255) / 256)), dim3(256), 0, st, (DictCell*)w.d_cells,
+                       (uint32_t)(d.cells.size() - 1), (const DictPatch*)w.d_list, (uint64_t)list.size());
+    if (hipGetLastError() != hipSuccess) return set_err(CC_ERR_HIP, "wire dictionary scatter launch");
+  }
+  HIPCHECK(hipStreamSynchronize(st));  // (the staged list leaves scope; the mirror may change after the call)
+  d.rebuilt = false;
+  d.dirty.clear();
+  d.pool_sent = d.pool.size();
+  return CC_OK;
+}
+
+// the attached dictionary serves this call: the same interner object the attach saw
+bool dict_serves(const cc_engine* e, const cc_wire_interner* in) {
+  return e->wdict && e->wdict->in == in && e->wdict->serial == wire_interner_info(in).serial;
+}
+
 }  // namespace
 
 int launch_wire_decode(const WireArgs& a, hipStream_t st) {
   if (a.n == 0) return 0;
   const uint64_t tiles = (a.n + kWireTile - 1) / kWireTile;
   if (tiles > 0x7FFFFFFFull) return -1;
-  hipLaunchKernelGGL(k_wire_decode, dim3((uint32_t)tiles), dim3(kWireLanes), 0, st, a);
+  if (a.dict.cells) hipLaunchKernelGGL(k_wire_decode<true>, dim3((uint32_t)tiles), dim3(kWireLanes), 0, st, a);
+  else hipLaunchKernelGGL(k_wire_decode<false>, dim3((uint32_t)tiles), dim3(kWireLanes), 0, st, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -284,6 +403,11 @@ int wire_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* i
     d_sch = e->wr_buf[kWrSchema];
     if (!e->wr_pin) HIPCHECK(hipHostMalloc((void**)&e->wr_pin, 64, hipHostMallocDefault));
     TRY(wire_table(e, st));
+    if (dict_serves(e, in)) {
+      TRY(wire_dict_update(e, in, st));
+      a.dict = DictView{(const DictCell*)e->wdict->d_cells, (const uint64_t*)e->wdict->d_pool,
+                        (uint32_t)(e->wdict->host.cells.size() - 1), e->wdict->first};
+    }
     for (hipEvent_t& ev : e->wr_ev)
       if (!ev) HIPCHECK(hipEventCreate(&ev));
     HIPCHECK(hipEventRecord(e->wr_ev[0], st));
@@ -301,9 +425,10 @@ int wire_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* i
     HIPCHECK(hipEventRecord(e->wr_ev[1], st));
     if (launch_wire_decode(a, st)) return set_err(CC_ERR_HIP, "wire decode launch", hipGetLastError());
     HIPCHECK(hipEventRecord(e->wr_ev[2], st));
-    HIPCHECK(hipMemcpyAsync(e->wr_pin, d_esc, 8, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(e->wr_pin, d_esc, 16, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     esc_n = e->wr_pin[0];
+    if (a.dict.cells) e->wdict->last_str_rows = e->wr_pin[1];
     if (esc_n) {
       esc.resize(words);
       HIPCHECK(hipMemcpyAsync(esc.data(), a.esc, 8 * words, hipMemcpyDeviceToHost, st));
@@ -362,7 +487,12 @@ int wire_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* i
                                                                    : "wire decode: entry ends past the buffer");
   }
   if (stop_row) *stop_row = stop;
+  const uint64_t hh_gen = e->hh_gen;
   TRY(wire_register_keys(e, in, skeys.data(), skeys.size()));
+  if (dict_serves(e, in) && e->wdict->hh_gen == hh_gen) {  // the only change of hh since the sync: set those key bits
+    wire_dict_mark_keys(e->wdict->host, e->wdict->first, skeys.data(), skeys.size());
+    e->wdict->hh_gen = e->hh_gen;
+  }
   *ctl_count = ctl.size();
   if (ctl.size() > ctl_cap) return set_err(CC_ERR_CAPACITY, "wire decode: more manager entries than h_ctl holds");
   if (!ctl.empty()) memcpy(h_ctl, ctl.data(), ctl.size() * sizeof(cc_wire_control));
@@ -375,6 +505,38 @@ extern "C" int cc_wire_timeline(cc_engine* e, float* h_ms) {
   if (!e || !h_ms) return set_err(CC_ERR_INVALID, "null argument");
   if (!e->wr_timed) return set_err(CC_ERR_STATE, "wire timeline: no decode has run on this engine");
   for (int k = 0; k < 3; ++k) HIPCHECK(hipEventElapsedTime(&h_ms[k], e->wr_ev[k], e->wr_ev[k + 1]));
+  return CC_OK;
+}
+
+extern "C" int cc_wire_dict_detach(cc_engine* e) {
+  if (!e) return set_err(CC_ERR_INVALID, "null argument");
+  if (!e->wdict) return CC_OK;
+  (void)hipSetDevice(e->device);
+  for (void* p : {e->wdict->d_cells, e->wdict->d_pool, e->wdict->d_list})
+    if (p) (void)hipFree(p);
+  delete e->wdict;
+  e->wdict = nullptr;
+  return CC_OK;
+}
+
+extern "C" int cc_wire_dict_attach(cc_engine* e, cc_wire_interner* in) {
+  if (!e || !in) return set_err(CC_ERR_INVALID, "wire dictionary: null argument");
+  HIPCHECK(hipSetDevice(e->device));
+  (void)cc_wire_dict_detach(e);
+  const WireInternerInfo info = wire_interner_info(in);
+  e->wdict = new WireDictDev{};
+  e->wdict->in = in, e->wdict->serial = info.serial, e->wdict->first = info.first;
+  const int rc = wire_dict_update(e, in, nullptr);
+  if (rc) (void)cc_wire_dict_detach(e);
+  return rc;
+}
+
+extern "C" int cc_wire_dict_get_info(cc_engine* e, cc_wire_dict_info* out) {
+  if (!e || !out) return set_err(CC_ERR_INVALID, "null argument");
+  if (!e->wdict) return set_err(CC_ERR_STATE, "wire dictionary: none is attached to this engine");
+  const WireDictDev& w = *e->wdict;
+  *out = cc_wire_dict_info{w.host.strings,  w.host.long_strings, w.host.pool.size() * 8, w.host.cells.size(),
+                           w.full_uploads, w.last_sync_strings,  w.last_str_rows};
   return CC_OK;
 }
 

@@ -9,6 +9,16 @@
 // identifier, an unknown id, truncation, trailing bytes, a manager entry (the registry).  The classifier is
 // conservative: whenever it says plain, decode_one returns CC_OK with the same columns (tests/fuzz/wire_plain_fuzz.cpp
 // holds it to that under AddressSanitizer).
+//
+// The String dictionary.  An engine may hold a device copy of an interner's Strings (cc_wire_dict_attach).  The parser
+// form that takes a dictionary (wire_parse<Bytes, DictView>) then also yields entries whose Strings are all known: a
+// String of at most CC_WIRE_STR_MAX bytes that the dictionary holds gives tag HANDLE and value first_handle + rank; as
+// a key it also needs the cell's "hash registered" bit.  The dictionary is an open-addressing table of DictCell (at
+// most half full, power-of-two cells, linear probing) over a byte pool in which every String starts 8-byte aligned
+// and is zero-padded to a multiple of 8 bytes.  dict_hash is the one definition of the hash; DictView::find the one
+// definition of the probe, for the host mirror (wire.cpp) and the kernel.  A hit is a hit only after the length and
+// every byte compare equal, so a resolved String is exactly the interner's (tests/fuzz/wire_str_fuzz.cpp runs both
+// with the hash cut to 4 bits).
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -156,6 +166,7 @@ static_assert(kWirePlainMax == 65, "the longest plain entry: 18 header bytes + M
 struct PlainRow {
   uint64_t iid, key, a, b, aux;
   uint8_t op, flags;
+  uint8_t strs;  // Strings resolved through the dictionary
 };
 
 // A byte accessor over host memory.  le64 / le32 assemble bytes [i, i + 8) / [i, i + 4) little-endian; the parser
@@ -173,18 +184,116 @@ struct HostBytes {
     for (int k = 3; k >= 0; --k) v = (v << 8) | p[i + k];
     return v;
   }
+  // bytes [i, i + n), n in 1..7, little-endian (reads no byte past them)
+  CC_WIRE_HD uint64_t lepart(uint32_t i, uint32_t n) const {
+    uint64_t v = 0;
+    for (uint32_t k = n; k-- > 0;) v = (v << 8) | p[i + k];
+    return v;
+  }
 };
 
 CC_WIRE_HD inline uint64_t wire_bswap64(uint64_t v) { return __builtin_bswap64(v); }
 CC_WIRE_HD inline uint32_t wire_bswap32(uint32_t v) { return __builtin_bswap32(v); }
 
+// ---- the String dictionary ---------------------------------------------------------------------------------------
+// One cell, 32 bytes, 32-byte aligned (one gather never straddles a cache line); the first 16 bytes decide nearly
+// every probe.
+struct alignas(32) DictCell {
+  uint64_t hash;   // dict_hash of the bytes
+  uint32_t len;    // UTF-8 bytes, <= CC_WIRE_STR_MAX
+  uint32_t flags;  // kDictUsed | kDictKeyReg
+  uint64_t off;    // of the String in the pool, a multiple of 8
+  uint32_t rank;   // handle - first_handle
+  uint32_t pad;
+};
+static_assert(sizeof(DictCell) == 32, "DictCell");
+enum : uint32_t { kDictUsed = 1u, kDictKeyReg = 2u };  // KeyReg: the handle's String.hashCode is registered on the engine
+
+// The hash of `n` bytes at `pos` behind the accessor: 8 bytes a step, the tail through lepart.
+// -DCC_WIRE_DICT_WEAK_HASH cuts it to 4 bits (a test build: nearly every probe then meets equal-hash cells).
+template <class Bytes>
+CC_WIRE_HD inline uint64_t dict_hash(const Bytes& s, uint32_t pos, uint32_t n) {
+  uint64_t h = 0x9E3779B97F4A7C15ull ^ ((uint64_t)n * 0xFF51AFD7ED558CCDull);
+  uint32_t i = 0;
+  for (; i + 8 <= n; i += 8) {
+    h = (h ^ s.le64(pos + i)) * 0xFF51AFD7ED558CCDull;
+    h ^= h >> 32;
+  }
+  if (i < n) {
+    h = (h ^ s.lepart(pos + i, n - i)) * 0xFF51AFD7ED558CCDull;
+    h ^= h >> 32;
+  }
+  h *= 0xC4CEB9FE1A85EC53ull;
+  h ^= h >> 29;
+#ifdef CC_WIRE_DICT_WEAK_HASH
+  h &= 15u;
+#endif
+  return h;
+}
+
+// The table as the parser reads it: the host mirror's vectors, or their device copies.
+struct DictView {
+  static constexpr bool kEnabled = true;
+  const DictCell* cells;  // [mask + 1]
+  const uint64_t* pool;   // the byte pool as 8-byte words
+  uint32_t mask;
+  uint64_t first;         // the interner's first handle
+  // the cell of bytes [pos, pos + n) behind `s` -> true, its rank and key bit
+  template <class Bytes>
+  CC_WIRE_HD bool find(const Bytes& s, uint32_t pos, uint32_t n, uint32_t& rank, bool& key_reg) const {
+    const uint64_t h = dict_hash(s, pos, n);
+    uint32_t at = (uint32_t)h & mask;
+    for (uint32_t probe = 0; probe <= mask; ++probe, at = (at + 1) & mask) {  // (at most half full: an empty cell ends it)
+      const DictCell& c = cells[at];
+      const uint32_t fl = c.flags;
+      if (!(fl & kDictUsed)) return false;
+      if (c.hash != h || c.len != n) continue;
+      const uint64_t* q = pool + (c.off >> 3);
+      bool same = true;
+      uint32_t i = 0;
+      for (; same && i + 8 <= n; i += 8) same = q[i >> 3] == s.le64(pos + i);
+      if (same && i < n) same = q[i >> 3] == s.lepart(pos + i, n - i);  // (the pool's padding is zero)
+      if (same) {
+        rank = c.rank;
+        key_reg = (fl & kDictKeyReg) != 0;
+        return true;
+      }
+    }
+    return false;
+  }
+};
+struct NoDict {  // the parser without a dictionary: a String escapes
+  static constexpr bool kEnabled = false;
+};
+
+// The longest entry the parser with a dictionary yields: as wire_plain_max, every writeObject field a String of
+// CC_WIRE_STR_MAX bytes behind a 4-byte id, a presence byte and an 8-byte length.
+constexpr uint32_t kWireStrValueMax = kWireIdMax + 1 + 8 + CC_WIRE_STR_MAX;
+constexpr uint32_t field_str_max(Field f) { return f == F_END ? 0u : (f == F_AUX || f == F_LKEY) ? 8u : kWireStrValueMax; }
+constexpr uint32_t wire_str_max() {
+  uint32_t m = 0;
+  for (const Schema& s : kSchema) {
+    uint32_t n = 0;
+    for (int k = 0; k < kSchemaFields && s.f[k] != F_END; ++k) n += field_str_max(s.f[k]);
+    m = n > m ? n : m;
+  }
+  return kWireIdMax + 8 + kWireIdMax + m;
+}
+constexpr uint32_t kWireStrEntryMax = wire_str_max();
+static_assert(kWireStrEntryMax == 18 + 3 * kWireStrValueMax + 8, "the longest entry: MAP_REPLACEIFPRESENT's three Strings");
+
 // One entry of `len` bytes behind `s` under codec `c`, with the schema words `sch` -> true: plain, `r` filled with the
 // host decoder's canonical values (Integer sign-extended, Boolean any nonzero byte -> 1, a null optional key -> key 0
 // and key tag 0, F_LKEY -> key tag LONG).  false: escape (r is unspecified).
-template <class Bytes>
-CC_WIRE_HD inline bool wire_plain_parse(const Bytes& s, uint32_t len, const cc_wire_codec& c, const uint32_t* sch,
-                                        PlainRow& r) {
-  if (len > kWirePlainMax) return false;
+// wire_parse is the parser; `d` is NoDict (a String escapes: wire_plain_parse) or a DictView.  With a dictionary a
+// String is read as wire.cpp's read_utf8 reads it: the optional presence byte (0: tag NULL, value 0), the length
+// (utf8_len_bytes in the codec's byte order), the bytes.  It yields tag HANDLE and first + rank when the dictionary
+// holds it; a String key (key tag 3) also needs the cell's key bit.  A length above CC_WIRE_STR_MAX or past the entry,
+// an unknown String and a key without the bit escape.  The parser never interns and never registers.
+template <class Bytes, class Dict>
+CC_WIRE_HD inline bool wire_parse(const Bytes& s, uint32_t len, const cc_wire_codec& c, const uint32_t* sch, const Dict& d,
+                                  PlainRow& r) {
+  if (len > (Dict::kEnabled ? kWireStrEntryMax : kWirePlainMax)) return false;
   const bool be = c.big_endian != 0;
   uint32_t pos = 0;
   // identifier + id (ids are signed, 1-4 bytes in the codec's byte order)
@@ -205,8 +314,11 @@ CC_WIRE_HD inline bool wire_plain_parse(const Bytes& s, uint32_t len, const cc_w
     pos += 8;
     return true;
   };
-  // serializer.writeObject(value) of a null / Long / Integer / Boolean
+  r.strs = 0;
+  bool key_reg = true;  // (of the value read last)
+  // serializer.writeObject(value) of a null / Long / Integer / Boolean, and with a dictionary a known String
   auto read_value = [&](uint32_t& tag, uint64_t& v) -> bool {
+    key_reg = true;
     if (pos >= len) return false;
     if (s.u8(pos) == kIdNull) {
       tag = CC_TAG_NULL, v = 0, pos += 1;
@@ -230,7 +342,29 @@ CC_WIRE_HD inline bool wire_plain_parse(const Bytes& s, uint32_t len, const cc_w
       tag = CC_TAG_BOOL, v = s.u8(pos) ? 1 : 0, pos += 1;
       return true;
     }
-    return false;  // a String, or a type with no canonical tag
+    if constexpr (Dict::kEnabled) {
+      if (id == c.id_string) {
+        if (c.utf8_presence_byte) {
+          if (pos >= len) return false;
+          if (!s.u8(pos++)) {
+            tag = CC_TAG_NULL, v = 0;
+            return true;
+          }
+        }
+        const uint32_t lw = c.utf8_len_bytes;
+        if (len - pos < lw) return false;
+        uint64_t n = lw == 8 ? s.le64(pos) : s.lepart(pos, lw);
+        if (be) n = wire_bswap64(n) >> (64 - 8 * lw);
+        pos += lw;
+        if (n > CC_WIRE_STR_MAX || len - pos < n) return false;
+        uint32_t rank = 0;
+        if (!d.find(s, pos, (uint32_t)n, rank, key_reg)) return false;
+        tag = CC_TAG_HANDLE, v = d.first + rank, pos += (uint32_t)n;
+        ++r.strs;
+        return true;
+      }
+    }
+    return false;  // a String without a dictionary, or a type with no canonical tag
   };
   int64_t top = 0, id = 0;
   if (!read_id(top) || (top != 30 && top != 31)) return false;
@@ -251,7 +385,8 @@ CC_WIRE_HD inline bool wire_plain_parse(const Bytes& s, uint32_t len, const cc_w
       if (tag == CC_TAG_NULL) {
         if (f == F_KEY) return false;
       } else {
-        kt = tag == CC_TAG_LONG ? 0u : tag == CC_TAG_INT ? 1u : 2u;
+        if (tag == CC_TAG_HANDLE && !key_reg) return false;  // the host registers the hash, then the bit is set
+        kt = tag == CC_TAG_LONG ? 0u : tag == CC_TAG_INT ? 1u : tag == CC_TAG_BOOL ? 2u : 3u;
         r.key = v;
       }
     } else if (f == F_A) {
@@ -268,6 +403,12 @@ CC_WIRE_HD inline bool wire_plain_parse(const Bytes& s, uint32_t len, const cc_w
   if (pos != len) return false;
   r.flags = CC_FLAGS(ta, tb, kt);
   return true;
+}
+
+template <class Bytes>
+CC_WIRE_HD inline bool wire_plain_parse(const Bytes& s, uint32_t len, const cc_wire_codec& c, const uint32_t* sch,
+                                        PlainRow& r) {
+  return wire_parse(s, len, c, sch, NoDict{}, r);
 }
 
 }  // namespace cc

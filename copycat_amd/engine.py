@@ -109,6 +109,9 @@ def lib():
             "cc_wire_decode": (i32, [P, P, P, P, u64, P, u64, P, P]),
             "cc_wire_decode_to_device": (i32, [P, P, P, P, u64, P, u64, P, P, P, u64, P, P, P, P]),
             "cc_wire_timeline": (i32, [P, P]),
+            "cc_wire_dict_attach": (i32, [P, P]),
+            "cc_wire_dict_detach": (i32, [P]),
+            "cc_wire_dict_get_info": (i32, [P, P]),
             "cc_apply_wire_host": (i32, [P, P, P, P, u64, P, u64, P, P, P, P, P, P]),
             "cc_split_batch": (i32, [P, u64, P, u32, u32, u32, P, P, P, P]),
             "cc_apply_batch_host_prefix": (i32, [P, P, u64, P, P, P]),

@@ -107,6 +107,25 @@ class WireDecoder:
             kind[ctl[k].row] = ctl[k].kind
         return DeviceBatch(cols, n), iid, kind, {k: int(getattr(stats, k)) for k in ("rows", "device_rows", "host_rows")}
 
+    def attach_dictionary(self):
+        """cc_wire_dict_attach: upload this decoder's interner to the engine as the device String dictionary; from
+        then on decode_to_device / Engine.apply_wire_host with this decoder resolve its known Strings on the GPU."""
+        assert self.engine is not None, "attach_dictionary needs an engine"
+        _check(lib().cc_wire_dict_attach(self.engine.h, self.interner.h))
+
+    def detach_dictionary(self):
+        """cc_wire_dict_detach: free the engine's dictionary (whichever decoder attached it)."""
+        assert self.engine is not None, "detach_dictionary needs an engine"
+        _check(lib().cc_wire_dict_detach(self.engine.h))
+
+    def dictionary_info(self):
+        """cc_wire_dict_get_info -> dict (strings, long_strings, pool_bytes, cells, full_uploads, last_sync_strings,
+        last_str_rows)"""
+        assert self.engine is not None, "dictionary_info needs an engine"
+        info = abi.cc_wire_dict_info()
+        _check(lib().cc_wire_dict_get_info(self.engine.h, C.byref(info)))
+        return {name: int(getattr(info, name)) for name, _ in abi.cc_wire_dict_info._fields_}
+
     def decode(self, entries=None, buf=None, offsets=None):
         buf, offsets = self._segment(entries, buf, offsets)
         n = len(offsets) - 1

@@ -645,7 +645,8 @@ int  cc_merge_results(const uint32_t* inst, uint64_t n, const uint8_t* rank_of_i
  * one lane per entry) decodes the PLAIN entries: InstanceCommand / InstanceQuery whose inner id is a known operation
  * and whose writeObject fields are all null / Long / Integer / Boolean under the codec.  Everything else ESCAPES to
  * the host decoder, in ascending row order, and its row is written over the device columns afterwards: entries that
- * carry a String (the interner is host state), the manager entries 35-38 (the registry is host state), and every
+ * carry a String (the interner is host state; but see "the device String dictionary" below, which resolves the
+ * Strings an attached interner already holds), the manager entries 35-38 (the registry is host state), and every
  * malformed entry (the host decoder words the error).  Instance ids resolve through a device hash table (id -> slot)
  * that the call rebuilds from the session registry whenever the registry has changed since the last call.
  * Not covered, as in cc_wire_decode: MessageBus operations and the TopicState class name stay undecoded (they escape
@@ -679,6 +680,38 @@ int  cc_wire_decode_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_
                               uint64_t buf_len, const uint64_t* h_offsets, uint64_t n, const cc_batch_out* d_cols,
                               uint64_t* d_iid, cc_wire_control* h_ctl, uint64_t ctl_cap, uint64_t* ctl_count,
                               cc_wire_stats* stats, void* stream, uint64_t* bad_row);
+/* ---- the device String dictionary (opt-in, per engine; symbols added under the unchanged CC_ABI_VERSION 6) ----
+ * After the first sight of a key universe nearly every String of a log is interned already, and looking those up
+ * needs no host state the device cannot hold.  cc_wire_dict_attach uploads the interner's Strings as a hash table
+ * plus a byte pool; from then on a decode on the device (cc_wire_decode_to_device, cc_apply_wire_host) that passes
+ * the same interner also decodes entries whose Strings are all in the dictionary, byte for byte as cc_wire_decode: a
+ * hit is a hit only after every byte compared equal, and the handle is first_handle + the String's rank.  What still
+ * escapes: a String the interner has not seen (its handle is its first-occurrence rank, which only the host decoder,
+ * going through the escaped rows in row order, can assign), a String longer than CC_WIRE_STR_MAX bytes, and a String
+ * KEY whose String.hashCode is not yet registered on this engine (cc_handle_hashes): the host fallback decodes that
+ * row and registers the hash as before, so the registered handles after a call are exactly cc_wire_decode's.  Every
+ * decode first brings the dictionary up to date with the interner (Strings interned by cc_wire_intern or by an
+ * earlier call's escapes) and with the engine's registered hashes (cc_handle_hashes, cc_snapshot_restore); the
+ * upload is the new pool bytes and the changed cells, the whole table only when it doubles.  A call that passes
+ * another interner (or one re-created at the same address) decodes as if nothing were attached.  The dictionary is
+ * no part of a snapshot; cc_engine_destroy detaches.  The interner must outlive the attachment or be detached first.
+ * CC_WIRE_STR_MAX: the decode hashes and compares a String in one lane, 8 bytes a step, so the bound caps the
+ * divergent loop at 32 steps and the longest device-decoded entry at 836 bytes, a twentieth of the kernel's LDS
+ * window; resource keys, member names and short messages are far below it, and a longer String is a payload whose
+ * host decode is small beside its upload. */
+#define CC_WIRE_STR_MAX 256
+typedef struct cc_wire_dict_info {
+  uint64_t strings;            /* Strings in the dictionary */
+  uint64_t long_strings;       /* Strings of the interner left out: longer than CC_WIRE_STR_MAX (or past rank 2^32 - 2) */
+  uint64_t pool_bytes;         /* the byte pool (every String padded to 8 bytes) */
+  uint64_t cells;              /* table cells (a power of two, at least twice `strings`) */
+  uint64_t full_uploads;       /* whole-table uploads so far (the attach, and every doubling) */
+  uint64_t last_sync_strings;  /* Strings added by the last sync (a decode syncs when the interner or the hashes moved) */
+  uint64_t last_str_rows;      /* rows of the last decode that the device decoded and that carried a resolved String */
+} cc_wire_dict_info;
+int  cc_wire_dict_attach(cc_engine* e, cc_wire_interner* in);
+int  cc_wire_dict_detach(cc_engine* e);   /* frees it; decodes behave as before the attach.  Harmless when not attached */
+int  cc_wire_dict_get_info(cc_engine* e, cc_wire_dict_info* out);  /* CC_ERR_STATE when nothing is attached */
 /* The stage times of the engine's last decode on the device (either call), from HIP events: h_ms[0] the H2D of the
  * bytes and offsets, h_ms[1] k_wire_decode, h_ms[2] the escape round trip (the count, and the bitmap when any row
  * escaped, back to the host); milliseconds.  The host fallback and the patch come after and are not in it. */

@@ -12,6 +12,17 @@ count back); its H2D, kernel and escape round trip from HIP events (cc_wire_time
 its algorithmic bytes (entry bytes + 8 B offset + 38 B of columns per row).  Median of --steps calls after --warmup.
 
     python scripts/wire_rate.py [--rows 16777216] [--instances 65536] [--steps 5] [--warmup 2] [--out FILE]
+
+--strings: the device String dictionary (cc_wire_dict_attach).  `--rows` MapCommands.Put entries of 53 bytes: a String
+key of 16 bytes drawn uniformly from `--keys` keys, a Long value, a ttl.  Two decoders on one engine hold the same
+Strings in two interners; one is attached as the dictionary, the other is not, and a call that passes an interner other
+than the attached one decodes as an unattached engine does (every row escapes to the host decoder: the behaviour before
+the dictionary).  After the parity check against cc_wire_decode the two are timed alternately in one run; one JSON line
+is appended to profiles/wire_gpu/rate_strings.json.
+
+--plain-ab: the default all-plain leg on the same engine through the attached and through the other decoder,
+alternating, --steps timed calls each: the attach must not move the plain kernel's time beyond the spread (max - min)
+of the unattached repeats.  One JSON line, profiles/wire_gpu/rate_plain_ab.json.
 """
 import argparse
 import json
@@ -40,15 +51,141 @@ def cas_stream(n, instances, id_first, seed=0xCA5):
     return e.reshape(-1), np.arange(n + 1, dtype=np.uint64) * ENTRY
 
 
+SENTRY, SKEY = 53, 16
+
+
+def put_stream(n, instances, id_first, keys, seed=0x57A):
+    """n MAP_PUT entries (String key, Long value, ttl) under the default codec -> (bytes, offsets, the keys' bytes)"""
+    from copycat_amd import abi
+
+    rng = np.random.default_rng(seed)
+    k = np.arange(keys, dtype=np.uint64)
+    table = np.zeros((keys, SKEY), np.uint8)
+    table[:, :4] = np.frombuffer(b"key-", np.uint8)
+    for d in range(12):
+        table[:, 4 + d] = 48 + (k // np.uint64(10 ** (11 - d))) % np.uint64(10)
+    e = np.zeros((n, SENTRY), np.uint8)
+    e[:, 0:2] = (1, 30)
+    e[:, 2:10] = (id_first + rng.integers(0, instances, n, dtype=np.uint64)).astype(">u8").view(np.uint8).reshape(n, 8)
+    e[:, 10:12] = (1, abi.CC_OP_MAP_PUT)
+    e[:, 12:18] = (2, abi.CC_WIRE_ID_STRING >> 8, abi.CC_WIRE_ID_STRING & 255, 1, 0, SKEY)
+    e[:, 18:34] = table[rng.integers(0, keys, n)]
+    e[:, 34:37] = (2, abi.CC_WIRE_ID_LONG >> 8, abi.CC_WIRE_ID_LONG & 255)
+    e[:, 37:45] = rng.integers(0, 1 << 20, n, dtype=np.uint64).astype(">u8").view(np.uint8).reshape(n, 8)
+    return e.reshape(-1), np.arange(n + 1, dtype=np.uint64) * SENTRY, table
+
+
+def same_columns(db, iid, bh, iidh):
+    import torch
+
+    ok = True
+    for name in ("inst", "op", "flags", "key", "a", "b", "aux"):
+        t = db.cols[name]
+        got = t.view({8: torch.int64, 4: torch.int32, 1: torch.uint8}[t.element_size()]).cpu().numpy()
+        ok = ok and np.array_equal(got.view(getattr(bh, name).dtype), getattr(bh, name))
+    return ok and np.array_equal(iid.view(torch.int64).cpu().numpy().view(np.uint64), iidh)
+
+
+def timed(E, D, buf, offs):
+    import torch
+
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    _, _, _, stats = D.decode_to_device(buf=buf, offsets=offs)
+    return (time.perf_counter() - t) * 1e3, E.wire_timeline(), stats
+
+
+def strings_leg(args):
+    import torch
+
+    from copycat_amd import abi
+    from copycat_amd.engine import Engine
+    from copycat_amd.wire import Interner, WireDecoder
+
+    n, R, K = args.rows, args.instances, args.keys
+    E = Engine(R, R, max(n, R), device=0)
+    E.resource_create_range(0, R, abi.CC_RES_VALUE)  # (the decode resolves instance ids, whatever their resource)
+    E.instance_open_range(0, R, 0, 1000, 7)
+    if args.strings:
+        buf, offs, table = put_stream(n, R, 1000, K)
+    else:
+        buf, offs = cas_stream(n, R, 1000)
+        table = put_stream(1, 1, 0, K)[2]
+    att, oth = WireDecoder(E, Interner(1)), WireDecoder(E, Interner(1))
+    t = time.perf_counter()
+    for row in table:
+        b = row.tobytes()
+        att.interner.intern(b)
+        oth.interner.intern(b)
+    intern_s = time.perf_counter() - t
+    t = time.perf_counter()
+    bh, iidh, kindh = oth.decode(buf=buf, offsets=offs)  # (registers every key's String.hashCode on the engine)
+    host_s = time.perf_counter() - t
+    att.attach_dictionary()
+    db, iid, kind, st0 = att.decode_to_device(buf=buf, offsets=offs)
+    ok = same_columns(db, iid, bh, iidh) and not kind.any()
+    del db, iid
+    db, iid, kind, st1 = oth.decode_to_device(buf=buf, offsets=offs)
+    ok = ok and same_columns(db, iid, bh, iidh) and not kind.any()
+    del db, iid, bh, iidh, kindh
+    runs = {"attached": [], "unattached": []}
+    for k in range(args.warmup + args.steps):
+        for name, D in (("unattached", oth), ("attached", att)):
+            r = timed(E, D, buf, offs)
+            if k >= args.warmup:
+                runs[name].append(r)
+    med = statistics.median
+    info = att.dictionary_info()
+    out = {"workload": ("MapCommands.Put entries, a 16-byte String key, a Long value, a ttl" if args.strings
+                        else "c2-shaped CompareAndSet entries, all plain"),
+           "rows": n, "instances": R, "keys": K, "entry_bytes": SENTRY if args.strings else ENTRY,
+           "parity_with_cc_wire_decode": bool(ok), "host_cc_wire_decode_s": round(host_s, 3),
+           "host_cc_wire_decode_rows_per_s_one_thread": n / host_s, "intern_s": round(intern_s, 3),
+           "dictionary": info, "table_bytes": info["cells"] * 32, "steps": args.steps, "gpu": torch.cuda.get_device_name(0)}
+    for name, rs in runs.items():
+        out[name] = {"call_ms": round(med(r[0] for r in rs), 3), "call_ms_min": round(min(r[0] for r in rs), 3),
+                     "call_ms_max": round(max(r[0] for r in rs), 3), "h2d_ms": round(med(r[1][0] for r in rs), 3),
+                     "kernel_ms": round(med(r[1][1] for r in rs), 4),
+                     "kernel_ms_all": [round(r[1][1], 4) for r in rs],
+                     "escape_round_trip_ms": round(med(r[1][2] for r in rs), 3),
+                     "host_rows": rs[-1][2]["host_rows"], "device_rows": rs[-1][2]["device_rows"]}
+    a, u = out["attached"], out["unattached"]
+    out["attached_over_unattached_call"] = round(a["call_ms"] / u["call_ms"], 4)
+    out["attached_kernel_within_its_h2d"] = bool(a["kernel_ms"] <= a["h2d_ms"])
+    spread = max(u["kernel_ms_all"]) - min(u["kernel_ms_all"])
+    out["unattached_kernel_spread_ms"] = round(spread, 4)
+    out["kernel_median_difference_ms"] = round(abs(a["kernel_ms"] - u["kernel_ms"]), 4)
+    if args.strings:
+        ok = ok and a["host_rows"] == 0 and a["call_ms"] < u["call_ms"]
+        if K <= 1024:  # the kernel's own bar, with the table in L2: the H2D of its input
+            ok = ok and out["attached_kernel_within_its_h2d"]
+    else:
+        out["plain_kernel_within_spread"] = bool(out["kernel_median_difference_ms"] <= spread)
+        ok = ok and out["plain_kernel_within_spread"]
+    line = json.dumps(out)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write(line + "\n")
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--strings", action="store_true")
+    ap.add_argument("--plain-ab", action="store_true")
+    ap.add_argument("--keys", type=int, default=1024)
     ap.add_argument("--rows", type=int, default=1 << 24)
     ap.add_argument("--instances", type=int, default=65536)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(HERE), "profiles", "wire_gpu", "rate.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    name = "rate_strings.json" if args.strings else "rate_plain_ab.json" if args.plain_ab else "rate.json"
+    args.out = args.out or os.path.join(os.path.dirname(HERE), "profiles", "wire_gpu", name)
     sys.path.insert(0, os.path.dirname(HERE))
+    if args.strings or args.plain_ab:
+        return strings_leg(args)
     import torch
 
     from copycat_amd import abi
