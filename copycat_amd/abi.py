@@ -273,6 +273,18 @@ class cc_wire_control(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("row", "kind", "key", "a", "b")]
 
 
+# cc_apply_wire_host_packed's input (include/copycat_apply.h "the log segment through the pipeline")
+class cc_wire_segment(C.Structure):
+    _fields_ = [
+        ("buf", C.c_void_p),
+        ("buf_len", C.c_uint64),
+        ("offsets", C.c_void_p),
+        ("n", C.c_uint64),
+        ("aux_blob", C.c_void_p),
+        ("aux_bytes", C.c_uint64),
+    ]
+
+
 class cc_wire_stats(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("rows", "device_rows", "host_rows")]
 

@@ -870,4 +870,101 @@ int wire_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* i
                    cc_wire_control* h_ctl, uint64_t ctl_cap, uint64_t* ctl_count, cc_wire_stats* stats, hipStream_t st,
                    uint64_t* bad_row, bool stop_at_ctl, uint64_t* stop_row);
 
+// ---- the wire segment as a source of the packed apply pipeline (cc_apply_wire_host_packed) ---------------------------
+// The chunk planner (wire.cpp; plain C++, no HIP call).  A segment of n entries is cut into chunks of whole
+// CC_PACK_BLOCK_ROWS blocks (the last one takes the tail): at most chunk_rows rows each, and shortened, block by block
+// but never below one block, until the chunk's byte span offsets[hi] - offsets[lo] is at most cap_bytes.  `ok` is the
+// end-offset check, offsets[lo] <= offsets[hi] <= buf_len: exactly when it holds, the copy of the chunk's byte span
+// stays inside the caller's buffer (the offsets between the two ends are then checked on the device).  When it fails
+// the planner scans the chunk as wire_to_device scans a segment: `send` = the rows before the first row i with
+// offsets[i + 1] < offsets[i] or offsets[i + 1] > buf_len (only those are copied, and the cap applies to their span);
+// otherwise send = hi - lo.
+constexpr uint64_t kWireChunkBytes = 1ull << 30;  // the staging cap of one chunk's entry bytes
+struct WireChunk {
+  uint64_t lo, hi;  // rows
+  uint64_t send;    // rows [lo, lo + send) are copied in
+  bool ok;
+};
+void wire_plan_chunks(const uint64_t* offsets, uint64_t n, uint64_t buf_len, uint64_t chunk_rows, uint64_t cap_bytes,
+                      std::vector<WireChunk>* out);
+// the first row i of [0, n) with offsets[i + 1] < offsets[i] or offsets[i + 1] > buf_len (n: none)
+uint64_t wire_first_bad_offset(const uint64_t* offsets, uint64_t n, uint64_t buf_len);
+
+// What wire_to_device and the pipeline's chunk decode share (wire_gpu.hip), one copy each.  wire_args: the codec
+// (null: the default) and the columns' pointers checked -> `a` with the codec, max_inst and the columns.
+int wire_args(cc_engine* e, const cc_wire_codec* codec, const cc_batch_out* d_cols, uint64_t* d_iid, WireArgs* a);
+// the attached dictionary brought up to date and into a->dict, when it serves `in` (else a->dict stays empty)
+int wire_args_dict(cc_engine* e, const cc_wire_interner* in, hipStream_t st, WireArgs* a);
+// The host fallback over the rows a decode left to the host.  `next` yields them in ascending order (~0: no more);
+// entry `row` is h_buf[h_offsets[row], h_offsets[row + 1]) and is reported as row_base + row.
+struct WireFallback {
+  std::vector<WirePatch> patch;      // rows as passed to `next`
+  std::vector<cc_wire_control> ctl;  // rows as reported
+  std::vector<uint64_t> skeys;       // String keys, registered on success
+  uint64_t fail_row = ~0ull, stop = ~0ull;  // as passed to `next`
+  int fail_rc = CC_OK;
+  bool stopped = false;
+};
+template <class Next>
+void wire_fallback(cc_engine* e, const cc_wire_codec& c, cc_wire_interner* in, const uint8_t* h_buf,
+                   const uint64_t* h_offsets, uint64_t row_base, bool stop_at_ctl, Next&& next, WireFallback* f) {
+  for (uint64_t row = next(); row != ~0ull; row = next()) {
+    WirePatch p{};
+    uint8_t kind = 0;
+    const cc_wire_out o{&p.inst, &p.iid, &p.op, &p.flags, &p.key, &p.a, &p.b, &p.aux, &kind};
+    const int rc = wire_decode_one(e, c, in, h_buf + h_offsets[row], h_buf + h_offsets[row + 1], row_base + row, 0, &o);
+    if (rc) {
+      f->fail_rc = rc, f->fail_row = row;
+      return;
+    }
+    p.row = row;
+    f->patch.push_back(p);
+    if (kind) {
+      f->ctl.push_back(cc_wire_control{row_base + row, kind, p.key, p.a, p.b});
+      if (stop_at_ctl) {
+        f->stopped = true, f->stop = row;
+        return;
+      }
+    } else if (CC_FLAG_KTAG(p.flags) == 3u) {
+      f->skeys.push_back(p.key);
+    }
+  }
+}
+// the escaped rows of a bitmap in ascending order, for wire_fallback
+struct EscRows {
+  const uint64_t* words;
+  uint64_t nwords, w = 0, bits = 0;
+  bool started = false;
+  uint64_t operator()() {
+    if (!started) started = true, bits = nwords ? words[0] : 0;
+    while (!bits) {
+      if (++w >= nwords) return ~0ull;
+      bits = words[w];
+    }
+    const uint64_t row = w * 64 + (uint64_t)__builtin_ctzll(bits);
+    bits &= bits - 1;
+    return row;
+  }
+};
+// the patch rows written over the columns on `st` (synchronous), and the String keys registered with the dictionary's
+// key bits kept current (the end of a decode that did not fail)
+int wire_patch_rows(cc_engine* e, const WireArgs& a, const std::vector<WirePatch>& patch, hipStream_t st);
+int wire_keys_done(cc_engine* e, cc_wire_interner* in, const std::vector<uint64_t>& skeys);
+// One chunk of the pipeline decoded on `st` (wire_gpu.hip).  d_off / d_bytes: the staged offsets[lo .. lo + send] and
+// bytes [offsets[lo], offsets[lo + send)) (both 16-byte aligned, the bytes padded as WireArgs asks).  The columns of
+// rows [0, *apply) of the chunk are final on return; *end: the call ends with this chunk, with *end_rc.
+struct WireChunkIn {
+  const cc_wire_codec* codec;
+  cc_wire_interner* in;
+  const uint8_t* h_buf;
+  uint64_t buf_len;
+  const uint64_t* h_offsets;  // the segment's
+  WireChunk c;
+  void* d_off;
+  void* d_bytes;
+  const cc_batch_out* d_cols;
+};
+int wire_chunk_decode(cc_engine* e, const WireChunkIn& in, hipStream_t st, uint64_t* apply, bool* end, int* end_rc,
+                      cc_wire_control* ctl, uint64_t* bad_row);
+
 }  // namespace cc

@@ -14,6 +14,7 @@
 // (cc_quorum_commit, cc_expire_sweep) and for hosts that keep columns resident.
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <string>
 
 #include <unordered_map>
@@ -1008,9 +1009,10 @@ extern "C" int cc_evpack_from_device(cc_engine* e, const cc_events* d, void* h_b
 }
 
 // ---- the packed apply pipeline -------------------------------------------------------------------------------------------
-// cc_apply_batch_host_packed, cc_apply_batch_host_packed_results and cc_apply_batch_host_packed_events are one chunked,
-// three-stream pipeline of a PCIe-inclusive step inside the library (pk_run); each entry point checks its own arguments,
-// says where results and events go (PkSink) and runs it:
+// cc_apply_batch_host_packed, cc_apply_batch_host_packed_results, cc_apply_batch_host_packed_events and
+// cc_apply_wire_host_packed are one chunked, three-stream pipeline of a PCIe-inclusive step inside the library
+// (pk_run); each entry point checks its own arguments, says where the rows come from (PkSource) and where results and
+// events go (PkSink), and runs it:
 //
 //   copy-in  (pk_in)      | H2D 0 | H2D 1 |        H2D 2        |
 //   engine   (own_stream)         | dec 0 + apply 0 [+ enc 0] | dec 1 + apply 1 [+ enc 1] | ... [| ev enc | ev D2H |]
@@ -1025,6 +1027,12 @@ extern "C" int cc_evpack_from_device(cc_engine* e, const cc_events* d, void* h_b
 // with an event sink every chunk runs under a device checkpoint (as the parts of cc_apply_batch_host_prefix): a chunk
 // that fails on a full event stream or map table region, and on nothing else, is rolled back and copied out nowhere;
 // a chunk that fails for any other reason stays applied and its rows are copied out before the call returns.
+//
+// Where the rows come from is a PkSource (below): the packed column blob of the three calls above (BlobSource), or a
+// wire segment (WireSource, cc_apply_wire_host_packed), whose chunk is its entry bytes, its offsets and its piece of the
+// aux blob (index / time), decoded by k_wire_decode after the offsets check on the device; a wire chunk may end the
+// call (a manager entry: the rows before it are applied; a row that fails to decode or an offsets violation: the
+// chunk is not applied).
 //
 // What the sinks change:
 //
@@ -1088,9 +1096,147 @@ int more_stamps(std::vector<hipEvent_t>* v, uint64_t want) {
   return CC_OK;
 }
 
-// rows [0, n) of a checked blob (n > 0, its columns `present`) applied chunk by chunk
-int pk_run(cc_engine* e, const void* h_blob, uint64_t n, uint32_t present, const cc_packed_opts* opts, const PkSink& o,
-           uint64_t* h_rows_done) {
+// the rows of a chunk: whole blocks within the caller's chunk_rows (0: 16 Mi), max_batch and one extended sub-batch (an
+// engine smaller than a block takes a block: a batch larger than max_batch then fails as it does in cc_apply_batch)
+uint64_t pk_chunk_rows(const cc_engine* e, const cc_packed_opts* opts) {
+  const uint64_t kB = CC_PACK_BLOCK_ROWS;
+  uint64_t chunk = opts && opts->chunk_rows ? opts->chunk_rows : (16ull << 20);
+  chunk = std::min<uint64_t>(chunk, 1ull << 40);
+  chunk = (chunk + kB - 1) / kB * kB;
+  const uint64_t cap_rows = std::max<uint64_t>(std::min(e->cfg.max_batch, e->sub_ext) / kB * kB, kB);
+  return std::min(chunk, cap_rows);
+}
+
+// Where a call's rows come from.  The pipeline asks a source for its cuts (whole blocks), has it put chunk k's input in
+// flight on the copy-in stream, and later, on the engine stream, has it leave chunk k's wide columns in the kHwCol
+// staging and say how many of the chunk's rows may be applied.
+struct PkSource {
+  // set by pk_run: record stamp `which` of chunk k on a stream (a no-op without CC_PACKED_TIMELINE)
+  std::function<hipError_t(uint64_t, uint64_t, hipStream_t)> stamp;
+  virtual ~PkSource() = default;
+  virtual uint64_t chunks() const = 0;
+  virtual uint64_t cut(uint64_t k) const = 0;  // the first row of chunk k; cut(chunks()) = n
+  virtual uint32_t present() const = 0;        // the wide columns it leaves
+  // chunk k's input on its way (stamps 0 and 1 around it, pk_landed[k & 1] behind it)
+  virtual int send(uint64_t k) = 0;
+  // The engine stream has waited for pk_landed[k & 1].  col: the staging columns of the chunk's rows.  *apply: rows
+  // [cut(k), cut(k) + *apply) are to be applied; *end: the call ends with this chunk, returning *end_rc (which, when
+  // not CC_OK, comes with *apply = 0: a chunk that fails in the source is not applied).
+  virtual int unpack(uint64_t k, void* const* col, uint64_t* apply, bool* end, int* end_rc) = 0;
+};
+
+// A checked cc_pack blob sent piecewise: the piece of the blocks of rows [lo, hi) is their directory entries, then
+// their data areas (contiguous, because offsets ascend with the block number), in one of two piece buffers.
+struct BlobPieces {
+  cc_engine* e;
+  const uint8_t* blob;
+  const cc_pack_header* hd;
+  const cc_pack_block* dir;
+  void* piece[2] = {};
+  uint64_t piece_base[2] = {}, piece_dir[2] = {};
+  BlobPieces(cc_engine* e_, const void* h_blob)
+      : e(e_), blob((const uint8_t*)h_blob), hd((const cc_pack_header*)h_blob),
+        dir((const cc_pack_block*)((const uint8_t*)h_blob + sizeof(cc_pack_header))) {}
+  int send(uint64_t k, uint64_t row_lo, uint64_t row_hi) {
+    const uint64_t kB = CC_PACK_BLOCK_ROWS;
+    const uint64_t b0 = row_lo / kB, b1 = std::min(hd->blocks, (row_hi + kB - 1) / kB);
+    const uint64_t lo = dir[b0].offset, hi = dir[b1 - 1].offset + dir[b1 - 1].bytes, db = (b1 - b0) * sizeof(cc_pack_block);
+    void* p = nullptr;
+    TRY(hw(e, kHwBlob0 + (int)(k & 1), db + (hi - lo), &p));
+    HIPCHECK(hipMemcpyAsync(p, dir + b0, db, hipMemcpyHostToDevice, e->pk_in));
+    if (hi > lo) HIPCHECK(hipMemcpyAsync((uint8_t*)p + db, blob + lo, hi - lo, hipMemcpyHostToDevice, e->pk_in));
+    piece[k & 1] = p, piece_base[k & 1] = lo, piece_dir[k & 1] = db;
+    return CC_OK;
+  }
+  int unpack(uint64_t k, uint64_t rows, void* const* col, uint32_t present) {
+    const int s = (int)(k & 1);
+    if (launch_unpack(unpack_args(piece[s], (const uint8_t*)piece[s] + piece_dir[s], piece_base[s], col, present),
+                      (uint32_t)((rows + CC_PACK_BLOCK_ROWS - 1) / CC_PACK_BLOCK_ROWS), e->own_stream))
+      return set_err(CC_ERR_HIP, "unpack launch", hipGetLastError());
+    return CC_OK;
+  }
+};
+
+// rows [0, n) of a checked blob (n > 0, its columns `present`) in chunks of `chunk` rows
+struct BlobSource : PkSource {
+  BlobPieces pieces;
+  uint64_t n, chunk;
+  uint32_t cols;
+  BlobSource(cc_engine* e, const void* h_blob, uint64_t n_, uint32_t present_, uint64_t chunk_)
+      : pieces(e, h_blob), n(n_), chunk(chunk_), cols(present_) {}
+  uint64_t chunks() const override { return (n + chunk - 1) / chunk; }
+  uint64_t cut(uint64_t k) const override { return std::min(n, k * chunk); }
+  uint32_t present() const override { return cols; }
+  int send(uint64_t k) override {
+    cc_engine* e = pieces.e;
+    HIPCHECK(stamp(k, 0, e->pk_in));
+    TRY(pieces.send(k, cut(k), cut(k + 1)));
+    HIPCHECK(stamp(k, 1, e->pk_in));
+    HIPCHECK(hipEventRecord(e->pk_landed[k & 1], e->pk_in));
+    return CC_OK;
+  }
+  int unpack(uint64_t k, void* const* col, uint64_t* apply, bool* end, int* end_rc) override {
+    *apply = cut(k + 1) - cut(k), *end = false, *end_rc = CC_OK;
+    return pieces.unpack(k, *apply, col, cols);
+  }
+};
+
+// A wire segment (cc_apply_wire_host_packed): the entries' bytes and offsets decoded on the GPU (wire_gpu.hip
+// wire_chunk_decode), index / time from the packed aux blob.  The cuts are the planner's (wire.cpp wire_plan_chunks):
+// whole blocks, at most the pipeline's chunk rows, shortened until a chunk's entry bytes are at most kWireChunkBytes
+// (1 GiB; a single block may exceed it).  Chunk k's staging (k & 1) holds its offsets, then (16-byte aligned) its bytes.
+enum WsSlot : int { kHwWire0 = kEpSlots, kHwWire1, kWsSlots };
+static_assert(kWsSlots <= 32, "cc_engine::hw_buf");
+
+struct WireSource : PkSource {
+  cc_engine* e;
+  const cc_wire_codec* codec;
+  cc_wire_interner* in;
+  const cc_wire_segment* seg;
+  BlobPieces aux;
+  uint32_t aux_present;
+  std::vector<WireChunk> plan;
+  void* stage[2] = {};
+  cc_wire_control* ctl;
+  uint64_t* bad_row;
+  WireSource(cc_engine* e_, const cc_wire_codec* codec_, cc_wire_interner* in_, const cc_wire_segment* seg_,
+             uint32_t aux_present_, uint64_t chunk, cc_wire_control* ctl_, uint64_t* bad_row_)
+      : e(e_), codec(codec_), in(in_), seg(seg_), aux(e_, seg_->aux_blob), aux_present(aux_present_), ctl(ctl_),
+        bad_row(bad_row_) {
+    wire_plan_chunks(seg->offsets, seg->n, seg->buf_len, chunk, kWireChunkBytes, &plan);
+  }
+  uint64_t chunks() const override { return plan.size(); }
+  uint64_t cut(uint64_t k) const override { return k < plan.size() ? plan[k].lo : seg->n; }
+  uint32_t present() const override { return aux_present | 0x1FC; }
+  static uint64_t off_bytes(uint64_t rows) { return (8 * (rows + 1) + 15) & ~15ull; }
+  int send(uint64_t k) override {
+    const WireChunk& c = plan[k];
+    const uint64_t* off = seg->offsets + c.lo;
+    const uint64_t span = off[c.send] - off[0];  // (the ends hold, or the planner's scan passed rows [lo, lo + send))
+    void* p = nullptr;
+    TRY(hw(e, kHwWire0 + (int)(k & 1), off_bytes(c.send) + ((span + 15) & ~15ull) + 16, &p));
+    stage[k & 1] = p;
+    HIPCHECK(stamp(k, 0, e->pk_in));
+    HIPCHECK(hipMemcpyAsync(p, off, 8 * (c.send + 1), hipMemcpyHostToDevice, e->pk_in));
+    if (span) HIPCHECK(hipMemcpyAsync((uint8_t*)p + off_bytes(c.send), seg->buf + off[0], span, hipMemcpyHostToDevice, e->pk_in));
+    TRY(aux.send(k, c.lo, c.hi));
+    HIPCHECK(stamp(k, 1, e->pk_in));
+    HIPCHECK(hipEventRecord(e->pk_landed[k & 1], e->pk_in));
+    return CC_OK;
+  }
+  int unpack(uint64_t k, void* const* col, uint64_t* apply, bool* end, int* end_rc) override {
+    const WireChunk& c = plan[k];
+    TRY(aux.unpack(k, c.hi - c.lo, col, aux_present));
+    const cc_batch_out cols{nullptr, nullptr, (uint32_t*)col[2], (uint8_t*)col[3], (uint8_t*)col[4],
+                            (uint64_t*)col[5], (uint64_t*)col[6], (uint64_t*)col[7], (uint64_t*)col[8]};
+    WireChunkIn w{codec, in, seg->buf, seg->buf_len, seg->offsets, c, stage[k & 1],
+                  (uint8_t*)stage[k & 1] + off_bytes(c.send), &cols};
+    return wire_chunk_decode(e, w, e->own_stream, apply, end, end_rc, ctl, bad_row);
+  }
+};
+
+// rows [0, n) of a source (n > 0) applied chunk by chunk
+int pk_run(cc_engine* e, PkSource& src, uint64_t n, const cc_packed_opts* opts, const PkSink& o, uint64_t* h_rows_done) {
   const bool res_blob = o.results == kResBlob, ev_host = o.events == kEvHost, ev_dev = o.events == kEvDevice;
   e->last_err_bits = 0;
   hipStream_t st = e->own_stream;
@@ -1100,14 +1246,8 @@ int pk_run(cc_engine* e, const void* h_blob, uint64_t n, uint32_t present, const
   if (ev_dev) TRY(ep_pin(e));
 
   const uint64_t kB = CC_PACK_BLOCK_ROWS;
-  uint64_t chunk = opts && opts->chunk_rows ? opts->chunk_rows : (16ull << 20);
-  chunk = std::min<uint64_t>(chunk, 1ull << 40);
-  chunk = (chunk + kB - 1) / kB * kB;
-  // whole blocks within max_batch and one extended sub-batch (an engine smaller than a block takes a block: a batch
-  // larger than max_batch then fails as it does in cc_apply_batch)
-  const uint64_t cap_rows = std::max<uint64_t>(std::min(e->cfg.max_batch, e->sub_ext) / kB * kB, kB);
-  chunk = std::min(chunk, cap_rows);
-  const uint64_t bpc = chunk / kB, nchunks = (n + chunk - 1) / chunk;
+  const uint64_t nchunks = src.chunks();
+  const uint32_t present = src.present();
   const bool ck = e->map_bits != 0 || o.events != kEvNone;  // as the parts of cc_apply_batch_host_prefix
   if (ck) TRY(ckpt_reserve(e));
   const bool stamps = opts && (opts->flags & CC_PACKED_TIMELINE);
@@ -1119,29 +1259,11 @@ int pk_run(cc_engine* e, const void* h_blob, uint64_t n, uint32_t present, const
   auto stamp = [&](uint64_t k, uint64_t which, hipStream_t s) -> hipError_t {
     return stamps ? hipEventRecord((*o.stamp)[per * k + which], s) : hipSuccess;
   };
+  src.stamp = stamp;
   cc_events acc{};  // kEvDevice: the call's events, in HBM
   if (ev_dev) TRY(ep_columns(e, o.ev_capacity, &acc));
   const uint64_t ev_cap = ev_host ? o.hev->capacity : o.ev_capacity;
-
-  const cc_pack_header* hd = (const cc_pack_header*)h_blob;
-  const uint8_t* const blob = (const uint8_t*)h_blob;
-  const cc_pack_block* const dir = (const cc_pack_block*)(blob + sizeof *hd);
-  void* piece[2] = {};
-  uint64_t piece_base[2] = {}, piece_dir[2] = {};
-  // chunk k's piece on its way: directory entries, then the data areas of its blocks
-  auto send = [&](uint64_t k) -> int {
-    const uint64_t b0 = k * bpc, b1 = std::min(hd->blocks, b0 + bpc);
-    const uint64_t lo = dir[b0].offset, hi = dir[b1 - 1].offset + dir[b1 - 1].bytes, db = (b1 - b0) * sizeof(cc_pack_block);
-    void* p = nullptr;
-    TRY(hw(e, kHwBlob0 + (int)(k & 1), db + (hi - lo), &p));
-    HIPCHECK(stamp(k, 0, e->pk_in));
-    HIPCHECK(hipMemcpyAsync(p, dir + b0, db, hipMemcpyHostToDevice, e->pk_in));
-    if (hi > lo) HIPCHECK(hipMemcpyAsync((uint8_t*)p + db, blob + lo, hi - lo, hipMemcpyHostToDevice, e->pk_in));
-    HIPCHECK(stamp(k, 1, e->pk_in));
-    HIPCHECK(hipEventRecord(e->pk_landed[k & 1], e->pk_in));
-    piece[k & 1] = p, piece_base[k & 1] = lo, piece_dir[k & 1] = db;
-    return CC_OK;
-  };
+  auto send = [&](uint64_t k) { return src.send(k); };
   // the result blob keeps the room of all n rows' directory entries; the data areas follow, chunk after chunk
   const uint64_t res_data0 = sizeof(cc_pack_header) + rp_blocks(n) * sizeof(cc_respack_block);
   uint64_t res_rows = 0, res_data = 0;  // rows whose results are on their way out, and their data bytes
@@ -1171,23 +1293,31 @@ int pk_run(cc_engine* e, const void* h_blob, uint64_t n, uint32_t present, const
   int rc = send(0);
   if (rc) return leave(rc);
   for (uint64_t k = 0; k < nchunks; ++k) {
-    const uint64_t lo = k * chunk, hi = std::min(n, lo + chunk), m = hi - lo;
+    const uint64_t lo = src.cut(k), rows = src.cut(k + 1) - lo;
     const int s = (int)(k & 1);
     if (k + 1 < nchunks && (rc = send(k + 1))) return leave(rc);
-    // decode: the wide columns of rows [lo, hi)
+    // decode: the wide columns of rows [lo, lo + rows)
     void* dcol[9] = {};
     for (int c = 0; c < 9; ++c)
-      if (((present >> c) & 1) && (rc = hw(e, kHwCol + c, kPkEsz[c] * m, &dcol[c]))) return leave(rc);
+      if (((present >> c) & 1) && (rc = hw(e, kHwCol + c, kPkEsz[c] * rows, &dcol[c]))) return leave(rc);
     const bool set1 = !res_blob && s;  // (only the wide sink has a second wide set)
     void *d_status, *d_value;
-    if ((rc = hw(e, set1 ? kHwStatus1 : kHwStatus, m, &d_status)) || (rc = hw(e, set1 ? kHwValue1 : kHwValue, 8 * m, &d_value)))
+    if ((rc = hw(e, set1 ? kHwStatus1 : kHwStatus, rows, &d_status)) ||
+        (rc = hw(e, set1 ? kHwValue1 : kHwValue, 8 * rows, &d_value)))
       return leave(rc);
     hipError_t x = hipStreamWaitEvent(st, e->pk_landed[s], 0);
     if (x == hipSuccess) x = stamp(k, 2, st);
     if (x != hipSuccess) return leave(set_err(CC_ERR_HIP, "packed apply: wait for the piece", x));
-    if (launch_unpack(unpack_args(piece[s], (const uint8_t*)piece[s] + piece_dir[s], piece_base[s], dcol, present),
-                      (uint32_t)((m + kB - 1) / kB), st))
-      return leave(set_err(CC_ERR_HIP, "unpack launch", hipGetLastError()));
+    // m: the rows of the chunk to apply (all of them, unless the source ends the call inside this chunk)
+    uint64_t m = 0;
+    bool src_end = false;
+    int src_rc = CC_OK;
+    if ((rc = src.unpack(k, dcol, &m, &src_end, &src_rc))) {
+      (void)hipStreamSynchronize(st);
+      return leave(rc);
+    }
+    if (src_end && (src_rc || m == 0)) return leave(src_rc);
+    const uint64_t hi = lo + m;
     x = stamp(k, 3, st);
     // sentinels as in apply_host.  Wide: result set s is prefilled again once its copy-out of chunk k - 2 is done.  Blob:
     // chunk k - 1's encode has read the one set on this stream
@@ -1294,6 +1424,7 @@ int pk_run(cc_engine* e, const void* h_blob, uint64_t n, uint32_t present, const
     ev_kept = ev_n;
     if (h_rows_done) *h_rows_done = hi;
     *o.chunks = stamps ? k + 1 : 0;
+    if (src_end) break;  // (the source's stop: a manager entry; the rows before it are applied)
   }
   return leave(CC_OK);
 }
@@ -1339,7 +1470,8 @@ extern "C" int cc_apply_batch_host_packed(cc_engine* e, const void* h_blob, uint
   o.results = kResWide, o.hout = hout;
   o.events = hev ? kEvHost : kEvNone, o.hev = hev;
   o.stamp = &e->pk_stamp, o.chunks = &e->pk_chunks;
-  return pk_run(e, h_blob, n, present, opts, o, h_rows_done);
+  BlobSource src(e, h_blob, n, present, pk_chunk_rows(e, opts));
+  return pk_run(e, src, n, opts, o, h_rows_done);
 }
 
 extern "C" int cc_apply_batch_host_packed_results(cc_engine* e, const void* h_blob, uint64_t bytes, void* h_res_blob,
@@ -1369,7 +1501,8 @@ extern "C" int cc_apply_batch_host_packed_results(cc_engine* e, const void* h_bl
   o.results = kResBlob, o.res = (uint8_t*)h_res_blob, o.res_bytes = res_bytes;
   o.events = hev ? kEvHost : kEvNone, o.hev = hev;
   o.stamp = &e->rp_stamp, o.chunks = &e->rp_chunks;
-  return pk_run(e, h_blob, n, present, opts, o, h_rows_done);
+  BlobSource src(e, h_blob, n, present, pk_chunk_rows(e, opts));
+  return pk_run(e, src, n, opts, o, h_rows_done);
 }
 
 extern "C" int cc_apply_batch_host_packed_events(cc_engine* e, const void* h_blob, uint64_t bytes, void* h_res_blob,
@@ -1407,7 +1540,70 @@ extern "C" int cc_apply_batch_host_packed_events(cc_engine* e, const void* h_blo
   o.results = kResBlob, o.res = (uint8_t*)h_res_blob, o.res_bytes = res_bytes;
   o.events = kEvDevice, o.ev_blob = h_ev_blob, o.ev_capacity = ev_capacity, o.ev_bytes = ev_bytes, o.ev_count = ev_count;
   o.stamp = &e->ep_stamp, o.chunks = &e->ep_chunks;
-  return pk_run(e, h_blob, n, present, opts, o, h_rows_done);
+  BlobSource src(e, h_blob, n, present, pk_chunk_rows(e, opts));
+  return pk_run(e, src, n, opts, o, h_rows_done);
+}
+
+// The log segment itself through the pipeline: a wire segment as the source, the result blob and (optionally) the
+// event blob as the sinks.
+extern "C" int cc_apply_wire_host_packed(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* in,
+                                         const cc_wire_segment* seg, void* h_res_blob, uint64_t res_cap,
+                                         uint64_t* res_bytes, void* h_ev_blob, uint64_t ev_capacity, uint64_t ev_cap_bytes,
+                                         uint64_t* ev_bytes, uint64_t* ev_count, const cc_packed_opts* opts,
+                                         uint64_t* h_rows_done, cc_wire_control* ctl, uint64_t* bad_row) {
+  if (h_rows_done) *h_rows_done = 0;
+  if (!e) return set_err(CC_ERR_INVALID, "result blob: null argument");
+  TRY(res_blob_ok(h_res_blob, res_bytes));
+  if (!in || !seg || !h_rows_done || !ctl || (seg->n && (!seg->buf || !seg->offsets || !seg->aux_blob)))
+    return set_err(CC_ERR_INVALID, "wire decode: null argument");
+  if (h_ev_blob) {
+    if (!ev_bytes || !ev_count) return set_err(CC_ERR_INVALID, "event blob: null argument");
+    if ((uintptr_t)h_ev_blob & 15) return set_err(CC_ERR_INVALID, "event blob: the blob must be 16-byte aligned");
+  }
+  if (opts && (opts->flags & ~(uint32_t)CC_PACKED_TIMELINE)) return set_err(CC_ERR_INVALID, "packed apply: unknown flag");
+  const uint64_t n = seg->n;
+  uint32_t present = 0;
+  if (n) {  // index (and time) of the n rows, in the packed format: checked before anything is copied or launched
+    uint64_t an = 0;
+    TRY(cc_pack_check(seg->aux_blob, seg->aux_bytes, &an, &present));
+    if (an != n) return set_err(CC_ERR_INVALID, "wire segment: the aux blob's row count differs from the segment's");
+    if (!(present & 1)) return set_err(CC_ERR_INVALID, "wire segment: the aux blob lacks the index column");
+    if (present & ~3u) return set_err(CC_ERR_INVALID, "wire segment: the aux blob holds a column other than index / time");
+  }
+  TRY(res_blob_room(n, res_cap, res_bytes));
+  if (h_ev_blob) {
+    uint64_t bound = 0;
+    TRY(cc_evpack_bound(ev_capacity, &bound));
+    if (ev_cap_bytes < bound) {
+      *ev_bytes = bound;
+      return set_err(CC_ERR_CAPACITY, "event blob: the blob buffer is smaller than cc_evpack_bound (*ev_bytes = the bound)");
+    }
+  }
+  if (codec && (codec->utf8_len_bytes < 1 || codec->utf8_len_bytes > 8))  // (wire_args' check, before anything is copied)
+    return set_err(CC_ERR_INVALID, "wire codec: utf8_len_bytes");
+  // from here on every return leaves a valid result blob of the rows copied out so far and a valid event blob
+  blob_header(kResultBlob, h_res_blob, 0, sizeof(cc_pack_header));
+  *res_bytes = sizeof(cc_pack_header);
+  if (h_ev_blob) {
+    blob_header(kEventBlob, h_ev_blob, 0, sizeof(cc_pack_header));
+    *ev_bytes = sizeof(cc_pack_header);
+    *ev_count = 0;
+  }
+  HIPCHECK(hipSetDevice(e->device));
+  e->rp_chunks = 0;
+  if (n == 0) return CC_OK;
+  PkSink o{};
+  o.results = kResBlob, o.res = (uint8_t*)h_res_blob, o.res_bytes = res_bytes;
+  o.events = h_ev_blob ? kEvDevice : kEvNone;
+  o.ev_blob = h_ev_blob, o.ev_capacity = ev_capacity, o.ev_bytes = ev_bytes, o.ev_count = ev_count;
+  o.stamp = &e->rp_stamp, o.chunks = &e->rp_chunks;  // (a result-blob call: the result-blob calls' stamps)
+  uint64_t scratch_bad = 0;
+  WireSource src(e, codec, in, seg, present, pk_chunk_rows(e, opts), ctl, bad_row ? bad_row : &scratch_bad);
+  return pk_run(e, src, n, opts, o, h_rows_done);
+}
+
+extern "C" int cc_wire_packed_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms) {
+  return cc_packed_results_timeline(e, cap, chunks, h_ms);  // (one stamp store for the engine's result-blob calls)
 }
 
 extern "C" int cc_packed_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms) {

@@ -462,3 +462,36 @@ extern "C" int cc_wire_decode(cc_engine* e, const cc_wire_codec* codec, cc_wire_
   }
   return CC_OK;
 }
+
+// ---- the chunk planner of cc_apply_wire_host_packed (engine_internal.h; plain C++, no HIP call) ----------------------
+uint64_t cc::wire_first_bad_offset(const uint64_t* offsets, uint64_t n, uint64_t buf_len) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i] || offsets[i + 1] > buf_len) return i;
+  return n;
+}
+
+void cc::wire_plan_chunks(const uint64_t* offsets, uint64_t n, uint64_t buf_len, uint64_t chunk_rows, uint64_t cap_bytes,
+                          std::vector<WireChunk>* out) {
+  const uint64_t kB = CC_PACK_BLOCK_ROWS;
+  chunk_rows = std::max<uint64_t>((chunk_rows + kB - 1) / kB * kB, kB);
+  auto ends_ok = [&](uint64_t lo, uint64_t hi) { return offsets[lo] <= offsets[hi] && offsets[hi] <= buf_len; };
+  out->clear();
+  for (uint64_t lo = 0; lo < n;) {
+    uint64_t hi = n - lo > chunk_rows ? lo + chunk_rows : n;
+    bool ok = ends_ok(lo, hi);
+    uint64_t send = hi - lo;
+    if (!ok) send = wire_first_bad_offset(offsets + lo, hi - lo, buf_len);
+    // rows [lo, lo + send) are in order and inside the buffer (checked by the scan) or bracketed by two checked ends
+    if (offsets[lo + send] - offsets[lo] > cap_bytes && hi - lo > kB) {
+      // the longest run of whole blocks, shorter than the rows to copy, whose ends hold and whose span fits; one block
+      // when none does
+      uint64_t h = lo + std::max((send - 1) / kB * kB, kB);
+      while (h > lo + kB && !(ends_ok(lo, h) && offsets[h] - offsets[lo] <= cap_bytes)) h -= kB;
+      hi = h;
+      ok = ends_ok(lo, hi);
+      send = ok ? hi - lo : wire_first_bad_offset(offsets + lo, hi - lo, buf_len);
+    }
+    out->push_back(WireChunk{lo, hi, send, ok});
+    lo = hi;
+  }
+}

@@ -46,6 +46,12 @@
 // spills, to VGPR lanes), no scratch, 29,504 B LDS, occupancy 5 waves / SIMD; k_wire_decode<true> 100 VGPRs, 106 SGPRs
 // (197 SGPR spills, to VGPR lanes), no scratch, 29,504 B LDS, occupancy 4 waves / SIMD; k_wire_patch 30 VGPRs,
 // k_dict_scatter 10 VGPRs, both no scratch, no LDS.
+//
+// The pipeline's chunk (cc_apply_wire_host_packed; host_path.hip WireSource, wire_chunk_decode below).  A chunk's
+// offsets are not scanned by the host: k_wire_offsets_check finds the first row whose end offset falls below its start
+// or lies past the chunk's staged span, k_wire_offsets_clamp rewrites the offsets after it, and only then k_wire_decode
+// runs, unchanged.  Resources (as above): k_wire_offsets_check 20 VGPRs, 30 SGPRs, k_wire_offsets_clamp 6 VGPRs,
+// 20 SGPRs; both no spills, no scratch, no LDS, occupancy 8 waves / SIMD.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -221,6 +227,51 @@ __global__ __launch_bounds__(256) void k_dict_scatter(DictCell* cells, uint32_t 
   cells[at] = list[i].cell;
 }
 
+// The offsets of one pipeline chunk checked on the device (cc_apply_wire_host_packed): off[0 .. n] are the chunk's
+// staged offsets, whose two ends the host checked (off[0] <= off[n] = span_end <= the buffer's length).  Lane t of a
+// block takes offsets 2t and 2t + 1 in one 16-byte load and its right neighbour's first offset by a shuffle (the last
+// lane of a wave reads it), so it judges rows 2t and 2t + 1; the first row i with off[i + 1] < off[i] or
+// off[i + 1] > span_end is kept per lane (rows ascend with the grid stride), reduced over the wave, and one atomicMin
+// per wave that found any goes to *bad (~0 before: no such row).
+__global__ __launch_bounds__(256) void k_wire_offsets_check(const uint64_t* off, uint64_t n, uint64_t span_end,
+                                                            unsigned long long* bad) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  unsigned long long first = ~0ull;
+  for (uint64_t base = (uint64_t)blockIdx.x * 256; 2 * base < n; base += stride) {  // (the same in every lane of a block)
+    const uint64_t p = base + threadIdx.x;
+    uint64_t x = 0, y = 0;
+    if (2 * p + 1 <= n) {
+      const ulonglong2 v = *(const ulonglong2*)(off + 2 * p);
+      x = v.x, y = v.y;
+    } else if (2 * p <= n) {
+      x = off[2 * p];
+    }
+    uint64_t z = __shfl_down((unsigned long long)x, 1);
+    if (lane == 63 && 2 * p + 2 <= n) z = off[2 * p + 2];
+    if (first != ~0ull) continue;
+    if (2 * p < n && (y < x || y > span_end)) first = 2 * p;
+    else if (2 * p + 1 < n && (z < y || z > span_end)) first = 2 * p + 1;
+  }
+  for (int d = 32; d; d >>= 1) {
+    const unsigned long long o = __shfl_xor(first, d);
+    first = o < first ? o : first;
+  }
+  if (lane == 0 && first != ~0ull) atomicMin(bad, first);
+}
+
+// Every offset after the row *bad rewritten to that row's start (*bad >= n: nothing to do).  The rows before it ascend
+// inside [off[0], span_end], so afterwards off[0 .. n] is non-decreasing and ends inside the staged span, whatever the
+// host passed.  k_wire_decode needs this: it forms its window addresses from the offsets alone (wbase from an entry's
+// start, the window's length from the group's last offset) and does not bound them by the staged span itself.  The
+// clamped entries are zero-length, escape, and the host discards their rows.
+__global__ __launch_bounds__(256) void k_wire_offsets_clamp(uint64_t* off, uint64_t n, const unsigned long long* bad) {
+  const uint64_t b = *bad;
+  if (b >= n) return;
+  const uint64_t v = off[b];  // (never written: only offsets after b are)
+  for (uint64_t j = b + 1 + (uint64_t)blockIdx.x * 256 + threadIdx.x; j <= n; j += (uint64_t)gridDim.x * 256) off[j] = v;
+}
+
 enum WrSlot : int { kWrBytes = 0, kWrOff, kWrEsc, kWrTable, kWrSchema, kWrPatch };
 
 // device buffer `slot` of the decoder with room for `bytes` (contents not kept; the calls are synchronous)
@@ -349,12 +400,7 @@ int launch_wire_patch(const WireArgs& a, const WirePatch* rows, uint64_t m, hipS
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int wire_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* in, const uint8_t* h_buf, uint64_t buf_len,
-                   const uint64_t* h_offsets, uint64_t n, const cc_batch_out* d_cols, uint64_t* d_iid,
-                   cc_wire_control* h_ctl, uint64_t ctl_cap, uint64_t* ctl_count, cc_wire_stats* stats, hipStream_t st,
-                   uint64_t* bad_row, bool stop_at_ctl, uint64_t* stop_row) {
-  if (!e || !in || !h_buf || !h_offsets || !d_cols || !ctl_count || (ctl_cap && !h_ctl))
-    return set_err(CC_ERR_INVALID, "wire decode: null argument");
+int wire_args(cc_engine* e, const cc_wire_codec* codec, const cc_batch_out* d_cols, uint64_t* d_iid, WireArgs* a) {
   void* const col[7] = {d_cols->inst, d_cols->op, d_cols->flags, d_cols->key, d_cols->a, d_cols->b, d_cols->aux};
   for (void* p : col)
     if (!p || ((uintptr_t)p & 15))
@@ -364,50 +410,98 @@ int wire_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* i
   if (codec) c = *codec;
   else cc_wire_codec_default(&c);
   if (c.utf8_len_bytes < 1 || c.utf8_len_bytes > 8) return set_err(CC_ERR_INVALID, "wire codec: utf8_len_bytes");
+  *a = WireArgs{};
+  a->codec = c;
+  a->max_inst = e->cfg.max_instances;
+  a->inst = (uint32_t*)col[0], a->op = (uint8_t*)col[1], a->flags = (uint8_t*)col[2];
+  a->key = (uint64_t*)col[3], a->a = (uint64_t*)col[4], a->b = (uint64_t*)col[5], a->aux = (uint64_t*)col[6];
+  a->iid = d_iid;
+  return CC_OK;
+}
+
+namespace {
+
+// what a decode needs on the device besides its input: the schema words, the pinned words and the instance table
+// (first use / when stale) -> a->schema and a->tbl_*
+int wire_args_device(cc_engine* e, hipStream_t st, WireArgs* a) {
+  void* d_sch;
+  if (!e->wr_buf[kWrSchema]) {
+    uint32_t sch[kSchemaIds];
+    schema_words(sch);
+    TRY(wr(e, kWrSchema, sizeof sch, &d_sch));
+    HIPCHECK(hipMemcpy(d_sch, sch, sizeof sch, hipMemcpyHostToDevice));
+  }
+  d_sch = e->wr_buf[kWrSchema];
+  if (!e->wr_pin) HIPCHECK(hipHostMalloc((void**)&e->wr_pin, 64, hipHostMallocDefault));
+  TRY(wire_table(e, st));
+  a->schema = (const uint32_t*)d_sch;
+  a->tbl_id = (const uint64_t*)e->wr_buf[kWrTable];
+  a->tbl_slot = (const uint32_t*)(a->tbl_id + (e->wr_mask + 1ull));
+  a->tbl_mask = e->wr_mask;
+  return CC_OK;
+}
+
+}  // namespace
+
+int wire_args_dict(cc_engine* e, const cc_wire_interner* in, hipStream_t st, WireArgs* a) {
+  a->dict = DictView{};
+  if (!dict_serves(e, in)) return CC_OK;
+  TRY(wire_dict_update(e, in, st));
+  a->dict = DictView{(const DictCell*)e->wdict->d_cells, (const uint64_t*)e->wdict->d_pool,
+                     (uint32_t)(e->wdict->host.cells.size() - 1), e->wdict->first};
+  return CC_OK;
+}
+
+int wire_patch_rows(cc_engine* e, const WireArgs& a, const std::vector<WirePatch>& patch, hipStream_t st) {
+  if (patch.empty()) return CC_OK;
+  void* d_patch;
+  TRY(wr(e, kWrPatch, patch.size() * sizeof(WirePatch), &d_patch));
+  HIPCHECK(hipMemcpyAsync(d_patch, patch.data(), patch.size() * sizeof(WirePatch), hipMemcpyHostToDevice, st));
+  if (launch_wire_patch(a, (const WirePatch*)d_patch, patch.size(), st))
+    return set_err(CC_ERR_HIP, "wire patch launch", hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(st));
+  return CC_OK;
+}
+
+int wire_keys_done(cc_engine* e, cc_wire_interner* in, const std::vector<uint64_t>& skeys) {
+  const uint64_t hh_gen = e->hh_gen;
+  TRY(wire_register_keys(e, in, skeys.data(), skeys.size()));
+  if (dict_serves(e, in) && e->wdict->hh_gen == hh_gen) {  // the only change of hh since the sync: set those key bits
+    wire_dict_mark_keys(e->wdict->host, e->wdict->first, skeys.data(), skeys.size());
+    e->wdict->hh_gen = e->hh_gen;
+  }
+  return CC_OK;
+}
+
+int wire_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* in, const uint8_t* h_buf, uint64_t buf_len,
+                   const uint64_t* h_offsets, uint64_t n, const cc_batch_out* d_cols, uint64_t* d_iid,
+                   cc_wire_control* h_ctl, uint64_t ctl_cap, uint64_t* ctl_count, cc_wire_stats* stats, hipStream_t st,
+                   uint64_t* bad_row, bool stop_at_ctl, uint64_t* stop_row) {
+  if (!e || !in || !h_buf || !h_offsets || !d_cols || !ctl_count || (ctl_cap && !h_ctl))
+    return set_err(CC_ERR_INVALID, "wire decode: null argument");
+  WireArgs a{};
+  TRY(wire_args(e, codec, d_cols, d_iid, &a));
   *ctl_count = 0;
   if (stop_row) *stop_row = n;
   if (stats) *stats = cc_wire_stats{n, 0, 0};
   if (n == 0) return CC_OK;
   HIPCHECK(hipSetDevice(e->device));
   // the rows before the first offsets violation go to the device (its row fails the call, unless a row before it does)
-  uint64_t m = n;
-  for (uint64_t i = 0; i < n; ++i)
-    if (h_offsets[i + 1] < h_offsets[i] || h_offsets[i + 1] > buf_len) {
-      m = i;
-      break;
-    }
-  WireArgs a{};
+  const uint64_t m = wire_first_bad_offset(h_offsets, n, buf_len);
   a.n = m;
-  a.codec = c;
-  a.max_inst = e->cfg.max_instances;
-  a.inst = (uint32_t*)col[0], a.op = (uint8_t*)col[1], a.flags = (uint8_t*)col[2];
-  a.key = (uint64_t*)col[3], a.a = (uint64_t*)col[4], a.b = (uint64_t*)col[5], a.aux = (uint64_t*)col[6];
-  a.iid = d_iid;
   std::vector<uint64_t> esc;  // the escape bitmap
   uint64_t esc_n = 0;
   if (m) {
     // staging: bytes [offsets[0], offsets[m]) at the start of a buffer padded to whole 16-byte loads, the offsets as
     // they are (the kernel subtracts offsets[0])
     const uint64_t span = h_offsets[m] - h_offsets[0];
-    void *d_bytes, *d_off, *d_esc, *d_sch;
+    void *d_bytes, *d_off, *d_esc;
     TRY(wr(e, kWrBytes, ((span + 15) & ~15ull) + 16, &d_bytes));
     TRY(wr(e, kWrOff, 8 * (m + 1), &d_off));
     const uint64_t words = (m + 63) / 64;
     TRY(wr(e, kWrEsc, 16 + 8 * words, &d_esc));  // the count, then (16-byte aligned) the bitmap
-    if (!e->wr_buf[kWrSchema]) {
-      uint32_t sch[kSchemaIds];
-      schema_words(sch);
-      TRY(wr(e, kWrSchema, sizeof sch, &d_sch));
-      HIPCHECK(hipMemcpy(d_sch, sch, sizeof sch, hipMemcpyHostToDevice));
-    }
-    d_sch = e->wr_buf[kWrSchema];
-    if (!e->wr_pin) HIPCHECK(hipHostMalloc((void**)&e->wr_pin, 64, hipHostMallocDefault));
-    TRY(wire_table(e, st));
-    if (dict_serves(e, in)) {
-      TRY(wire_dict_update(e, in, st));
-      a.dict = DictView{(const DictCell*)e->wdict->d_cells, (const uint64_t*)e->wdict->d_pool,
-                        (uint32_t)(e->wdict->host.cells.size() - 1), e->wdict->first};
-    }
+    TRY(wire_args_device(e, st, &a));
+    TRY(wire_args_dict(e, in, st, &a));
     for (hipEvent_t& ev : e->wr_ev)
       if (!ev) HIPCHECK(hipEventCreate(&ev));
     HIPCHECK(hipEventRecord(e->wr_ev[0], st));
@@ -416,10 +510,6 @@ int wire_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* i
     HIPCHECK(hipMemsetAsync(d_esc, 0, 16, st));
     a.bytes = (const uint8_t*)d_bytes;
     a.off = (const uint64_t*)d_off;
-    a.schema = (const uint32_t*)d_sch;
-    a.tbl_id = (const uint64_t*)e->wr_buf[kWrTable];
-    a.tbl_slot = (const uint32_t*)(a.tbl_id + (e->wr_mask + 1ull));
-    a.tbl_mask = e->wr_mask;
     a.esc_n = (unsigned long long*)d_esc;
     a.esc = (uint64_t*)d_esc + 2;
     HIPCHECK(hipEventRecord(e->wr_ev[1], st));
@@ -438,67 +528,113 @@ int wire_to_device(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* i
     e->wr_timed = true;
   }
   // the fallback: every escaped row through the host decoder, in ascending row order
-  std::vector<WirePatch> patch;
-  std::vector<cc_wire_control> ctl;
-  std::vector<uint64_t> skeys;  // String keys, registered on success
-  uint64_t fail_row = ~0ull, stop = n;
-  int fail_rc = CC_OK;
-  bool stopped = false;
-  patch.reserve(esc_n);
-  for (uint64_t w = 0; w < esc.size() && fail_rc == CC_OK && !stopped; ++w)
-    for (uint64_t bits = esc[w]; bits; bits &= bits - 1) {
-      const uint64_t row = w * 64 + (uint64_t)__builtin_ctzll(bits);
-      WirePatch p{};
-      uint8_t kind = 0;
-      const cc_wire_out o{&p.inst, &p.iid, &p.op, &p.flags, &p.key, &p.a, &p.b, &p.aux, &kind};
-      const int rc = wire_decode_one(e, c, in, h_buf + h_offsets[row], h_buf + h_offsets[row + 1], row, 0, &o);
-      if (rc) {
-        fail_rc = rc, fail_row = row;
-        break;
-      }
-      p.row = row;
-      patch.push_back(p);
-      if (kind) {
-        ctl.push_back(cc_wire_control{row, kind, p.key, p.a, p.b});
-        if (stop_at_ctl) {
-          stopped = true, stop = row;
-          break;
-        }
-      } else if (CC_FLAG_KTAG(p.flags) == 3u) {
-        skeys.push_back(p.key);
-      }
-    }
-  if (!patch.empty()) {
-    void* d_patch;
-    TRY(wr(e, kWrPatch, patch.size() * sizeof(WirePatch), &d_patch));
-    HIPCHECK(hipMemcpyAsync(d_patch, patch.data(), patch.size() * sizeof(WirePatch), hipMemcpyHostToDevice, st));
-    if (launch_wire_patch(a, (const WirePatch*)d_patch, patch.size(), st))
-      return set_err(CC_ERR_HIP, "wire patch launch", hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(st));
+  WireFallback f;
+  f.patch.reserve(esc_n);
+  wire_fallback(e, a.codec, in, h_buf, h_offsets, 0, stop_at_ctl, EscRows{esc.data(), esc.size()}, &f);
+  TRY(wire_patch_rows(e, a, f.patch, st));
+  if (stats) stats->host_rows = f.patch.size(), stats->device_rows = m - std::min<uint64_t>(m, esc_n);
+  if (f.fail_rc) {  // (cc_last_error holds decode_one's "wire row N: ...")
+    if (bad_row) *bad_row = f.fail_row;
+    return f.fail_rc;
   }
-  if (stats) stats->host_rows = patch.size(), stats->device_rows = m - std::min<uint64_t>(m, esc_n);
-  if (fail_rc) {  // (cc_last_error holds decode_one's "wire row N: ...")
-    if (bad_row) *bad_row = fail_row;
-    return fail_rc;
-  }
-  if (!stopped && m < n) {
+  if (!f.stopped && m < n) {
     if (bad_row) *bad_row = m;
     return set_err(CC_ERR_INVALID, h_offsets[m + 1] < h_offsets[m] ? "wire decode: offsets decrease"
                                                                    : "wire decode: entry ends past the buffer");
   }
-  if (stop_row) *stop_row = stop;
-  const uint64_t hh_gen = e->hh_gen;
-  TRY(wire_register_keys(e, in, skeys.data(), skeys.size()));
-  if (dict_serves(e, in) && e->wdict->hh_gen == hh_gen) {  // the only change of hh since the sync: set those key bits
-    wire_dict_mark_keys(e->wdict->host, e->wdict->first, skeys.data(), skeys.size());
-    e->wdict->hh_gen = e->hh_gen;
-  }
-  *ctl_count = ctl.size();
-  if (ctl.size() > ctl_cap) return set_err(CC_ERR_CAPACITY, "wire decode: more manager entries than h_ctl holds");
-  if (!ctl.empty()) memcpy(h_ctl, ctl.data(), ctl.size() * sizeof(cc_wire_control));
+  if (stop_row) *stop_row = f.stopped ? f.stop : n;
+  TRY(wire_keys_done(e, in, f.skeys));
+  *ctl_count = f.ctl.size();
+  if (f.ctl.size() > ctl_cap) return set_err(CC_ERR_CAPACITY, "wire decode: more manager entries than h_ctl holds");
+  if (!f.ctl.empty()) memcpy(h_ctl, f.ctl.data(), f.ctl.size() * sizeof(cc_wire_control));
   return CC_OK;
 }
 
+// One chunk of cc_apply_wire_host_packed, as wire_to_device decodes a segment, with the offsets scan on the device:
+// the dictionary sync, the offsets check and clamp, k_wire_decode, ONE read-back (escape count, dictionary counter and
+// the first bad offset row together in the pinned words), then the host fallback in row order and the patch.  The
+// dictionary sync before each chunk lets a String first seen in chunk k resolve on the device in chunk k + 1;
+// exactness does not depend on it: an unresolved String escapes, and the host fallback gives it the same handle.
+int wire_chunk_decode(cc_engine* e, const WireChunkIn& in, hipStream_t st, uint64_t* apply, bool* end, int* end_rc,
+                      cc_wire_control* ctl, uint64_t* bad_row) {
+  const WireChunk& c = in.c;
+  const uint64_t rows = c.hi - c.lo, s = c.send;
+  const uint64_t* off = in.h_offsets + c.lo;
+  *apply = 0, *end = false, *end_rc = CC_OK;
+  WireArgs a{};
+  TRY(wire_args(e, in.codec, in.d_cols, nullptr, &a));
+  a.n = s;
+  std::vector<uint64_t> esc;
+  uint64_t esc_n = 0, dev_bad = ~0ull;
+  if (s) {
+    void* d_esc;
+    const uint64_t words = (s + 63) / 64;
+    TRY(wr(e, kWrEsc, 32 + 8 * words, &d_esc));  // escape count, dictionary counter, first bad offset row; the bitmap
+    TRY(wire_args_device(e, st, &a));
+    TRY(wire_args_dict(e, in.in, st, &a));
+    HIPCHECK(hipMemsetAsync(d_esc, 0, 16, st));
+    HIPCHECK(hipMemsetAsync((uint8_t*)d_esc + 16, 0xFF, 16, st));
+    a.bytes = (const uint8_t*)in.d_bytes;
+    a.off = (const uint64_t*)in.d_off;
+    a.esc_n = (unsigned long long*)d_esc;
+    a.esc = (uint64_t*)d_esc + 4;
+    unsigned long long* d_bad = (unsigned long long*)d_esc + 2;
+    const uint32_t cb = (uint32_t)std::min<uint64_t>(1024, (s / 2 + 256) / 256);
+    hipLaunchKernelGGL(k_wire_offsets_check, dim3(cb), dim3(256), 0, st, a.off, s, off[s], d_bad);
+    hipLaunchKernelGGL(k_wire_offsets_clamp, dim3((uint32_t)std::min<uint64_t>(256, (s + 256) / 256)), dim3(256), 0, st,
+                       (uint64_t*)in.d_off, s, (const unsigned long long*)d_bad);
+    if (hipGetLastError() != hipSuccess) return set_err(CC_ERR_HIP, "wire offsets check launch");
+    if (launch_wire_decode(a, st)) return set_err(CC_ERR_HIP, "wire decode launch", hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(e->wr_pin, d_esc, 32, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    esc_n = e->wr_pin[0];
+    if (a.dict.cells) e->wdict->last_str_rows = e->wr_pin[1];
+    dev_bad = e->wr_pin[2];
+    if (esc_n) {
+      esc.resize(words);
+      HIPCHECK(hipMemcpyAsync(esc.data(), a.esc, 8 * words, hipMemcpyDeviceToHost, st));
+      HIPCHECK(hipStreamSynchronize(st));
+    }
+  }
+  // m: the first offsets violation of the chunk as wire_to_device finds it (rows: none).  The device's check is the
+  // stricter one (an offset past the chunk's own end, though inside the buffer, is caught where it rises, the host's
+  // where it falls again), so when it reports a row the host scans this one chunk itself, and the rows between the
+  // two, which were not decoded on the device, go through the host decoder with the escaped ones.
+  uint64_t m = c.ok ? rows : s, lim = s, extra = ~0ull;
+  if (dev_bad < s) {
+    m = wire_first_bad_offset(off, rows, in.buf_len);
+    if (!c.ok || m < dev_bad || m >= rows)
+      return set_err(CC_ERR_STATE, "internal check: the device offsets check disagrees with the host scan");
+    lim = extra = dev_bad;
+  }
+  WireFallback f;
+  EscRows er{esc.data(), esc.size()};
+  bool esc_done = false;
+  auto next = [&]() -> uint64_t {
+    if (!esc_done) {
+      const uint64_t r = er();
+      if (r != ~0ull && r < lim) return r;
+      esc_done = true;
+    }
+    return extra < m ? extra++ : ~0ull;
+  };
+  wire_fallback(e, a.codec, in.in, in.h_buf, off, c.lo, true, next, &f);
+  TRY(wire_patch_rows(e, a, f.patch, st));
+  if (f.fail_rc) {  // (cc_last_error holds decode_one's "wire row N: ...", N a segment row)
+    *end = true, *end_rc = f.fail_rc, *bad_row = c.lo + f.fail_row;
+    return CC_OK;
+  }
+  if (!f.stopped && m < rows) {
+    *end = true, *bad_row = c.lo + m;
+    *end_rc = set_err(CC_ERR_INVALID, off[m + 1] < off[m] ? "wire decode: offsets decrease"
+                                                           : "wire decode: entry ends past the buffer");
+    return CC_OK;
+  }
+  TRY(wire_keys_done(e, in.in, f.skeys));
+  *apply = f.stopped ? f.stop : rows;
+  if (f.stopped) *end = true, *ctl = f.ctl.back();
+  return CC_OK;
+}
 }  // namespace cc
 
 extern "C" int cc_wire_timeline(cc_engine* e, float* h_ms) {

@@ -140,6 +140,8 @@ def lib():
             "cc_evpack_from_device": (i32, [P, P, P, u64, P, P, P]),
             "cc_apply_batch_host_packed_events": (i32, [P, P, u64, P, u64, P, P, u64, u64, P, P, P, P]),
             "cc_packed_events_timeline": (i32, [P, u64, P, P]),
+            "cc_apply_wire_host_packed": (i32, [P, P, P, P, P, u64, P, P, u64, u64, P, P, P, P, P, P]),
+            "cc_wire_packed_timeline": (i32, [P, u64, P, P]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -396,6 +398,67 @@ class Engine:
         if m < n:
             control = {k: int(getattr(ctl, k)) for k in ("row", "kind", "key", "a", "b")}
         return status[:m], value[:m], {k: v[:count.value] for k, v in ev.items()}, m, control
+
+    def apply_wire_host_packed(self, decoder, index, time=None, entries=None, buf=None, offsets=None, capacity=None,
+                               chunk_rows=0, timeline=False, events=True, out=None, ev_out=None, aux=None):
+        """cc_apply_wire_host_packed: apply_wire_host through the chunk pipeline -> (result_blob, event_blob, ev_count,
+        rows_done, ctl).  index / time travel as a packed blob (batch.pack); batch.unpack_results(result_blob) and
+        batch.unpack_events(event_blob) give the rows and events (pos = segment rows) of the chunks applied.  ctl is
+        None, or the manager entry at row rows_done as a dict (row, kind, key, a, b): the host runs it and calls again
+        from row rows_done + 1.  A call that stops at a chunk on a capacity returns normally with rows_done < n and
+        ctl None; a decode failure raises EngineError with .bad_row, .rows_done and the two blobs attached.
+        events=False: no event stream (event_blob is None).  `out` / `ev_out`: 16-byte-aligned uint8 buffers of at
+        least batch.results_bound(n) / batch.events_bound(capacity) bytes (e.g. page-locked with host_register).
+        `aux`: the packed index / time blob itself (index and time are then ignored), e.g. packed once and page-locked."""
+        from .batch import Batch, pack
+
+        buf, offsets = decoder._segment(entries, buf, offsets, check=False)
+        n = len(offsets) - 1
+        if aux is None:
+            b = Batch(n)
+            b.index[:] = np.ascontiguousarray(index, np.uint64)
+            if time is not None:
+                b.time[:] = np.ascontiguousarray(time, np.uint64)
+            aux = pack(b, columns=("index",) if time is None else ("index", "time"))
+        seg = abi.cc_wire_segment(buf.ctypes.data, buf.size, offsets.ctypes.data, n, aux.ctypes.data, aux.nbytes)
+        return self._wire_packed(decoder, seg, n, capacity, chunk_rows, timeline, events, out, ev_out, (buf, offsets, aux))
+
+    def _wire_packed(self, decoder, seg, n, capacity, chunk_rows, timeline, events, out, ev_out, keep):
+        from .batch import _aligned_bytes, events_bound, results_bound
+
+        cap = capacity if capacity is not None else max(4 * n, 1024)
+        res = out if out is not None else _aligned_bytes(results_bound(n))
+        evb = None
+        if events:
+            evb = ev_out if ev_out is not None else _aligned_bytes(events_bound(cap))
+        opts = abi.cc_packed_opts(chunk_rows=chunk_rows, flags=abi.CC_PACKED_TIMELINE if timeline else 0)
+        done, size, ev_size, ev_count, bad = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        ctl = abi.cc_wire_control()
+        rc = self.L.cc_apply_wire_host_packed(self.h, C.byref(decoder.codec), decoder.interner.h, C.byref(seg),
+                                              res.ctypes.data, res.nbytes, C.byref(size),
+                                              evb.ctypes.data if events else None, cap, evb.nbytes if events else 0,
+                                              C.byref(ev_size), C.byref(ev_count), C.byref(opts), C.byref(done),
+                                              C.byref(ctl), C.byref(bad))
+        blobs_ok = size.value <= res.nbytes and (not events or ev_size.value <= evb.nbytes)
+        rblob = res[:size.value] if blobs_ok else None
+        eblob = evb[:ev_size.value] if events and blobs_ok else None
+        if rc != abi.CC_OK and not (rc == abi.CC_ERR_CAPACITY and done.value < n and blobs_ok):
+            err = EngineError(rc, lib().cc_last_error().decode(errors="replace"))
+            err.bad_row, err.rows_done, err.result_blob, err.event_blob = bad.value, done.value, rblob, eblob
+            err.ev_count = ev_count.value
+            raise err
+        control = None
+        if rc == abi.CC_OK and done.value < n:
+            control = {k: int(getattr(ctl, k)) for k in ("row", "kind", "key", "a", "b")}
+        return rblob, eblob, ev_count.value, done.value, control
+
+    def wire_packed_timeline(self):
+        """Per chunk of the last apply_wire_host_packed(timeline=True): (H2D, decode, apply, encode, D2H) ms."""
+        n = C.c_uint64()
+        _check(self.L.cc_wire_packed_timeline(self.h, 0, C.byref(n), None))
+        ms = np.zeros((max(n.value, 1), 5), np.float32)
+        _check(self.L.cc_wire_packed_timeline(self.h, n.value, C.byref(n), _np(ms)))
+        return ms[:n.value]
 
     def wire_timeline(self):
         """cc_wire_timeline: (H2D, kernel, escape round trip) milliseconds of the last decode on the device."""

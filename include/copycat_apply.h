@@ -721,7 +721,8 @@ int  cc_wire_timeline(cc_engine* e, float* h_ms);
  * from row r + 1: the rows after a manager entry must see the registry it leaves behind, and only the Strings of
  * rows <= r are interned.  h_index / h_time: the entries' log indices / times (h_time may be NULL); results and
  * events return to the host as from cc_apply_batch_host_events (h_events may be NULL: then as cc_apply_batch_host),
- * under its size rules, for rows [0, r).  Not pipelined: one upload, one decode, one apply. */
+ * under its size rules, for rows [0, r).  One upload, one decode, one apply, wide results back: a host that hands over
+ * whole segments calls cc_apply_wire_host_packed (below, after the packed formats), which pipelines the same work. */
 int  cc_apply_wire_host(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* in, const uint8_t* h_buf,
                         uint64_t buf_len, const uint64_t* h_offsets, uint64_t n, const uint64_t* h_index,
                         const uint64_t* h_time, const cc_results* h_out, const cc_events* h_events,
@@ -1004,6 +1005,51 @@ int  cc_apply_batch_host_packed_events(cc_engine* e, const void* h_blob, uint64_
  * D2H, event encode, event D2H milliseconds.  The event blob is encoded and sent once per call: the last two figures
  * are the call's, repeated in every chunk's row. */
 int  cc_packed_events_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms);
+
+/* ---- the log segment through the pipeline: wire bytes in, packed results and events out (host_path.hip, wire_gpu.hip) --
+ * cc_apply_wire_host, cut into the chunks of the packed pipeline: while chunk k is decoded (k_wire_decode) and applied,
+ * chunk k + 1's entry bytes, offsets and its piece of the aux blob travel H2D, and chunk k - 1's encoded results travel
+ * D2H.  The wire does not carry index and time: they arrive as a cc_pack_batch blob of n rows whose present columns are
+ * index, or index | time (cc_pack_check runs first; another row count, no index, or any other column: CC_ERR_INVALID
+ * before anything is copied).  Results leave as a packed result blob, events as a packed event blob (h_ev_blob NULL: no
+ * event stream, a publishing op fails its chunk as in cc_apply_batch_host); the blob arguments follow
+ * cc_apply_batch_host_packed_events, bounds and checks included.  opts: chunk_rows and CC_PACKED_TIMELINE.
+ *
+ * Chunks are whole CC_PACK_BLOCK_ROWS blocks (a block is two CC_WIRE_TILE_ROWS tiles), at most chunk_rows rows, and
+ * shortened, block by block but never below one block, until a chunk's entry bytes are at most 1 GiB (the staging cap).
+ * With the segment cut that way, state, results (cc_respack_unpack), events (cc_evpack_unpack, pos = segment rows), the
+ * applied index, the interner, the registered String.hashCodes, *ctl and the error are what consecutive
+ * cc_apply_wire_host calls over those chunks produce; rows are reported as segment rows (ctl->row, *bad_row and the
+ * "wire row N" of cc_last_error).  Neither blob's bytes depend on chunk_rows.
+ *   manager entry at row r   CC_OK, *h_rows_done = r, *ctl = the entry; rows [0, r) are applied and in the blobs;
+ *                            nothing of a later row is applied, interned or registered.  Call again from row r + 1.
+ *   an entry that fails to decode, or an offsets violation (offsets decrease, an entry ends past buf_len)
+ *                            its chunk is not applied: the error of cc_wire_decode_to_device, *bad_row = the row,
+ *                            *h_rows_done = the rows of the chunks before, both blobs valid for exactly those rows.
+ *                            The host checks only a chunk's two end offsets before its copy; the offsets between them
+ *                            are checked on the device, so no byte outside [buf, buf + buf_len) is ever read.
+ *   full event stream or map table region
+ *                            CC_ERR_CAPACITY, the chunk rolled back, as cc_apply_batch_host_packed_events.
+ *   n == 0                   CC_OK, header-only blobs, nothing launched.
+ * When *h_rows_done < n and the call returned CC_OK, *ctl is the manager entry; otherwise *ctl is not written.  Every
+ * stream is drained before the call returns.  Page-lock buf, offsets and the blobs or the copies do not overlap. */
+typedef struct cc_wire_segment {
+  const uint8_t*  buf;       uint64_t buf_len;   /* entry bytes, no alignment needed            */
+  const uint64_t* offsets;   uint64_t n;         /* n + 1 offsets into buf                      */
+  const void*     aux_blob;  uint64_t aux_bytes; /* cc_pack_batch blob of n rows, present =     */
+                                                 /* index, or index | time; 16-byte aligned     */
+} cc_wire_segment;
+int  cc_apply_wire_host_packed(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* in,
+                               const cc_wire_segment* seg, void* h_res_blob, uint64_t res_cap, uint64_t* res_bytes,
+                               void* h_ev_blob, uint64_t ev_capacity, uint64_t ev_cap_bytes, uint64_t* ev_bytes,
+                               uint64_t* ev_count, const cc_packed_opts* opts, uint64_t* h_rows_done,
+                               cc_wire_control* ctl, uint64_t* bad_row);
+/* The stage times of the last cc_apply_wire_host_packed call made with CC_PACKED_TIMELINE: *chunks = the chunks that
+ * completed; h_ms (5 floats per chunk, room for cap chunks) = H2D, decode (dictionary sync, offsets check, kernel,
+ * read-back and host fallback), apply, encode, D2H milliseconds.  The call is a result-blob call of the pipeline and
+ * keeps its stamps where cc_apply_batch_host_packed_results keeps its own: either timeline call reports the engine's
+ * last call of either kind. */
+int  cc_wire_packed_timeline(cc_engine* e, uint64_t cap, uint64_t* chunks, float* h_ms);
 
 #ifdef __cplusplus
 }

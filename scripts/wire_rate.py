@@ -23,6 +23,13 @@ is appended to profiles/wire_gpu/rate_strings.json.
 --plain-ab: the default all-plain leg on the same engine through the attached and through the other decoder,
 alternating, --steps timed calls each: the attach must not move the plain kernel's time beyond the spread (max - min)
 of the unattached repeats.  One JSON line, profiles/wire_gpu/rate_plain_ab.json.
+
+--pipeline: cc_apply_wire_host against cc_apply_wire_host_packed on the default segment, every host buffer page-locked,
+on one engine pair (the serial call on one, the pipelined call on the other, both fed the same rows).  The two are
+called alternately, --steps timed calls each after --warmup; after every pair the unpacked results equal the serial
+call's rows, and at the end the two engines' values and applied indices are equal.  The pipelined call runs at the
+default chunk_rows and, as a second setting reported beside it, at --chunk-rows (default 2 Mi): one JSON line with both
+medians, the ratios and the per-chunk timeline (H2D, decode, apply, encode, D2H), profiles/wire_gpu/rate_pipeline.json.
 """
 import argparse
 import json
@@ -170,10 +177,103 @@ def strings_leg(args):
     return 0 if ok else 1
 
 
+def pipeline_leg(args):
+    import ctypes as C
+
+    import torch
+
+    from copycat_amd import abi
+    from copycat_amd.batch import Batch, _aligned_bytes, pack, pack_bound, results_bound, unpack_results
+    from copycat_amd.engine import Engine, host_register
+    from copycat_amd.wire import Interner, WireDecoder
+
+    n, R = args.rows, args.instances
+    buf, offs = cas_stream(n, R, 1000)
+    engines = []
+    for _ in range(2):
+        E = Engine(R, R, max(n, R), device=0)
+        E.resource_create_range(0, R, abi.CC_RES_VALUE)
+        E.instance_open_range(0, R, 0, 1000, 7)
+        engines.append((E, WireDecoder(E, Interner(1))))
+    (Es, Ds), (Ep, Dp) = engines
+    status, value = np.zeros(n, np.uint8), np.zeros(n, np.uint64)
+    index = np.zeros(n, np.uint64)
+    res, aux = _aligned_bytes(results_bound(n)), _aligned_bytes(pack_bound(n, columns=("index",)))
+    for a in (buf, offs, status, value, index, res, aux):
+        host_register(a)
+    r = abi.cc_results(status.ctypes.data, value.ctypes.data)
+    applied, ctl = C.c_uint64(), abi.cc_wire_control()
+    calls = 0
+
+    def next_index():
+        nonlocal calls
+        index[:] = np.arange(1 + calls * n, 1 + (calls + 1) * n, dtype=np.uint64)
+        calls += 1
+        b = Batch(0)
+        b.index = index
+        b.op = index  # (only its length is read)
+        return pack(b, columns=("index",), out=aux)
+
+    def serial():
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        rc = Es.L.cc_apply_wire_host(Es.h, C.byref(Ds.codec), Ds.interner.h, buf.ctypes.data, buf.size, offs.ctypes.data, n,
+                                     index.ctypes.data, None, C.byref(r), None, C.byref(applied), C.byref(ctl))
+        dt = (time.perf_counter() - t) * 1e3
+        assert rc == 0 and applied.value == n, (rc, applied.value)
+        return dt
+
+    def piped(blob, chunk_rows):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = Ep.apply_wire_host_packed(Dp, None, buf=buf, offsets=offs, aux=blob, chunk_rows=chunk_rows, events=False,
+                                        out=res, timeline=True)
+        dt = (time.perf_counter() - t) * 1e3
+        assert out[3] == n and out[4] is None, out[3:]
+        return dt, out[0], Ep.wire_packed_timeline()
+
+    settings = (("default", 0), (f"chunk_rows_{args.chunk_rows}", args.chunk_rows))
+    runs = {"serial": []}
+    ok = True
+    for k in range(args.warmup + args.steps):
+        for name, chunk_rows in settings:
+            blob = next_index()
+            ts = serial()
+            tp, rblob, tl = piped(blob, chunk_rows)
+            s2, v2 = unpack_results(rblob)
+            ok = ok and np.array_equal(s2, status) and np.array_equal(v2, value)
+            if k >= args.warmup:
+                runs["serial"].append(ts)
+                runs.setdefault(name, []).append((tp, tl, int(rblob.nbytes)))
+    ok = ok and Es.applied_index() == Ep.applied_index() == calls * n
+    ok = ok and all(np.array_equal(x, y) for x, y in zip(Es.value_state(), Ep.value_state()))
+    med = statistics.median
+    out = {"workload": "c2-shaped CompareAndSet entries, all plain, decoded and applied", "rows": n, "instances": R,
+           "entry_bytes": ENTRY, "results_and_state_equal": bool(ok), "steps": args.steps,
+           "serial_call_ms": round(med(runs["serial"]), 3), "serial_call_ms_all": [round(x, 3) for x in runs["serial"]],
+           "serial_result_bytes": 9 * n, "gpu": torch.cuda.get_device_name(0)}
+    for name, _ in settings:
+        rs = runs[name]
+        tl = rs[-1][1]
+        out[name] = {"call_ms": round(med(x[0] for x in rs), 3), "call_ms_all": [round(x[0], 3) for x in rs],
+                     "over_serial": round(med(x[0] for x in rs) / med(runs["serial"]), 4), "chunks": int(len(tl)),
+                     "result_blob_bytes": rs[-1][2], "h2d_ms_sum": round(float(tl[:, 0].sum()), 3),
+                     "call_over_h2d_sum": round(med(x[0] for x in rs) / max(float(tl[:, 0].sum()), 1e-9), 3),
+                     "timeline_ms_h2d_decode_apply_encode_d2h": [[round(float(x), 3) for x in row] for row in tl]}
+    line = json.dumps(out)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--strings", action="store_true")
     ap.add_argument("--plain-ab", action="store_true")
+    ap.add_argument("--pipeline", action="store_true")
+    ap.add_argument("--chunk-rows", type=int, default=2 << 20)
     ap.add_argument("--keys", type=int, default=1024)
     ap.add_argument("--rows", type=int, default=1 << 24)
     ap.add_argument("--instances", type=int, default=65536)
@@ -181,11 +281,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    name = "rate_strings.json" if args.strings else "rate_plain_ab.json" if args.plain_ab else "rate.json"
+    name = ("rate_strings.json" if args.strings else "rate_plain_ab.json" if args.plain_ab
+            else "rate_pipeline.json" if args.pipeline else "rate.json")
     args.out = args.out or os.path.join(os.path.dirname(HERE), "profiles", "wire_gpu", name)
     sys.path.insert(0, os.path.dirname(HERE))
     if args.strings or args.plain_ab:
         return strings_leg(args)
+    if args.pipeline:
+        return pipeline_leg(args)
     import torch
 
     from copycat_amd import abi
