@@ -268,6 +268,9 @@ class cc_wire_out(C.Structure):
 # the GPU wire decoder (include/copycat_apply.h "the same decode on the GPU"; copycat_amd/csrc/wire_gpu.hip)
 CC_WIRE_TILE_ROWS = 2048
 
+# the device split (include/copycat_apply.h "the same split and merge on the device"; copycat_amd/csrc/split_gpu.hip)
+CC_SPLIT_TILE_ROWS = 4096
+
 
 class cc_wire_control(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("row", "kind", "key", "a", "b")]

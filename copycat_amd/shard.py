@@ -107,6 +107,118 @@ def merge_by_owner(inst, inst_owner, world, parts, threads=0):
     return status, value
 
 
+# ---- the same split and merge for columns that are already in HBM (cc_split_batch_device, split_gpu.hip) ------------
+def _owner_tensor(own_dev, world, device):
+    """The owner table as a uint8 device tensor (a host table is validated and converted as _rank_table does)."""
+    import torch
+
+    if isinstance(own_dev, torch.Tensor):
+        if own_dev.dtype != torch.uint8 or not own_dev.is_cuda or not own_dev.is_contiguous():
+            raise ValueError("own_dev must be a contiguous uint8 device tensor")
+        if not 1 <= world <= 256:
+            raise ValueError("world must be in [1, 256]")
+        return own_dev
+    return torch.from_numpy(_rank_table(own_dev, world)).to(device)
+
+
+def _split_workspace(n, world, device):
+    import torch
+
+    from .engine import _check, lib
+
+    need = C.c_uint64()
+    _check(lib().cc_split_device_bound(n, world, C.byref(need)))
+    return torch.empty(need.value, dtype=torch.uint8, device=device)
+
+
+def _stream_on(stream, device):
+    import torch
+
+    return stream if stream is not None else torch.cuda.current_stream(device)
+
+
+def split_counts_device(db, own_dev, world, stream=None):
+    """Rows per rank of a stable split of device columns (cc_split_batch_device with no outputs)."""
+    from .engine import _check, _dptr, _np, _stream_ptr, lib
+
+    inst = db.cols["inst"]
+    tab = _owner_tensor(own_dev, world, inst.device)
+    st = _stream_on(stream, inst.device)
+    work = _split_workspace(db.n, world, inst.device)
+    counts = np.zeros(world, np.uint64)
+    cols = db.struct()
+    _check(lib().cc_split_batch_device(C.byref(cols), db.n, _dptr(tab) if tab.numel() else None, tab.numel(), world,
+                                       None, None, _np(counts), None, _dptr(work), work.numel(), _stream_ptr(st)))
+    return counts
+
+
+def split_batch_device(db, own_dev, world, rows=False, stream=None):
+    """Stable split of a DeviceBatch into per-rank DeviceBatches, all in HBM (cc_split_batch_device).
+
+    Returns [(rows, DeviceBatch)] indexed by rank; rows[r] (a uint64 device tensor, None if rows=False) are the rank's
+    rows of `db` in log order: they map a rank's event `pos` back to log rows.  A column `db` lacks, the parts lack.
+    The outputs are complete on return (the stream is synchronised)."""
+    import torch
+
+    from .engine import DeviceBatch, _check, _dptr, _np, _stream_ptr, lib
+
+    inst = db.cols["inst"]
+    dev = inst.device
+    tab = _owner_tensor(own_dev, world, dev)
+    st = _stream_on(stream, dev)
+    counts = split_counts_device(db, tab, world, stream=st)
+    work = _split_workspace(db.n, world, dev)
+    outs = (abi.cc_batch_out * world)()
+    rowp = (C.c_void_p * world)()
+    parts = []
+    with torch.cuda.stream(st):
+        for r in range(world):
+            c = int(counts[r])
+            cols = {name: torch.empty(c, dtype=db.cols[name].dtype, device=dev)
+                    for name, _ in abi.BATCH_COLUMNS if db.cols.get(name) is not None}
+            for name, t in cols.items():
+                setattr(outs[r], name, t.data_ptr() if c else None)
+            ridx = torch.empty(c, dtype=torch.uint64, device=dev) if rows else None
+            rowp[r] = ridx.data_ptr() if rows and c else None
+            parts.append((ridx, DeviceBatch(cols, c)))
+    cap = counts.copy()
+    cols = db.struct()
+    _check(lib().cc_split_batch_device(C.byref(cols), db.n, _dptr(tab) if tab.numel() else None, tab.numel(), world, outs,
+                                       _np(cap), _np(counts), rowp if rows else None, _dptr(work), work.numel(),
+                                       _stream_ptr(st)))
+    st.synchronize()
+    return parts
+
+
+def merge_by_owner_device(inst, own_dev, world, parts, stream=None):
+    """parts[r] = (status, value) device tensors of rank r, in its split order -> (status[n], value[n]) device tensors
+    in log order (cc_merge_results_device; `inst` is the uint32 device column the split used).  The outputs are
+    complete on return (the stream is synchronised)."""
+    import torch
+
+    from .engine import _check, _dptr, _stream_ptr, lib
+
+    dev = inst.device
+    tab = _owner_tensor(own_dev, world, dev)
+    st = _stream_on(stream, dev)
+    n = inst.numel()
+    work = _split_workspace(n, world, dev)
+    with torch.cuda.stream(st):
+        status = torch.empty(n, dtype=torch.uint8, device=dev)
+        value = torch.empty(n, dtype=torch.uint64, device=dev)
+    pr = (abi.cc_results * world)()
+    for r, (s, v) in enumerate(parts):
+        if s.dtype != torch.uint8 or v.element_size() != 8 or not (s.is_contiguous() and v.is_contiguous()):
+            raise ValueError("parts must be (uint8 status, 64-bit value) contiguous device tensors")
+        pr[r].status = s.data_ptr() if s.numel() else None
+        pr[r].value = v.data_ptr() if v.numel() else None
+    out = abi.cc_results(status.data_ptr() if n else None, value.data_ptr() if n else None)
+    _check(lib().cc_merge_results_device(_dptr(inst) if n else None, n, _dptr(tab) if tab.numel() else None, tab.numel(),
+                                         world, pr, C.byref(out), _dptr(work), work.numel(), _stream_ptr(st)))
+    st.synchronize()
+    return status, value
+
+
 def merge_results(n, parts):
     """parts: [(rows, status, value)] -> (status[n], value[n]) in log order."""
     status = np.zeros(n, np.uint8)

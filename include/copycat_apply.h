@@ -637,6 +637,48 @@ int  cc_split_batch(const cc_batch* in, uint64_t n, const uint8_t* rank_of_inst,
 int  cc_merge_results(const uint32_t* inst, uint64_t n, const uint8_t* rank_of_inst, uint32_t n_inst, uint32_t world,
                       uint32_t threads, const cc_results* parts, const cc_results* out);
 
+/* ---- the same split and merge on the device: columns in HBM in, per-rank columns in HBM out (split_gpu.hip) --------
+ * These calls exist from this commit on, under the unchanged CC_ABI_VERSION 6 (symbols are only added).
+ * For a host whose columns are already in device memory (cc_wire_decode_to_device, cc_unpack_to_device, an upload):
+ * cc_split_batch_device / cc_merge_results_device are cc_split_batch / cc_merge_results item by item, byte for byte,
+ * with these differences:
+ *   - d_in, outs[r], parts[r], d_out and d_rows are host structs / host arrays as above, whose members are device
+ *     pointers, as are d_rank_of_inst and d_inst.  counts and out_cap are host memory.
+ *   - No engine is involved (as cc_quorum_commit); the calls run on the device that owns `stream` (the current
+ *     device for the null stream).  There is no `threads`.
+ *   - d_work: caller-owned device scratch (16-byte aligned; cc_device_alloc, a torch tensor) of at least
+ *     cc_split_device_bound(n, world) bytes; a smaller work_bytes is CC_ERR_INVALID.  The bound is host arithmetic:
+ *     no HIP call, usable on a machine without a GPU.
+ *   - Every input column that is present must be 16-byte aligned (CC_ERR_INVALID otherwise); outputs need only their
+ *     natural alignment.  Inputs, outputs and the workspace must not overlap.
+ *   - Every argument check that does not need the counts runs before the first HIP call.
+ * Unchanged: world in [1, 256]; inst is required, any other input column may be NULL and its outputs are then left
+ * alone; inst >= n_inst goes to rank 0 (n_inst == 0 with a NULL table: everything does); a rank's output columns may
+ * be NULL when its count is 0; outs == NULL computes the counts only; counts[r] > out_cap[r] is CC_ERR_CAPACITY with
+ * `counts` filled and nothing written to any output; an owner byte >= world is CC_ERR_INVALID with nothing written;
+ * d_rows (optional, world device pointers, each optional) receives each output row's source row as u64.
+ * Synchronisation: the call waits on the host exactly once, after the count and the scan kernels, for `world` counts
+ * and one error word.  On CC_OK the scatter (the merge: the gather) is enqueued on `stream` and NOT waited for: the
+ * outputs are ordered on `stream`, as after cc_apply_batch, and the inputs and d_work must stay untouched until the
+ * stream has passed them.  A counts-only call waits and enqueues nothing.
+ * Peer memory: an output pointer may be any memory the device can store to, the peer-mapped HBM of another GPU
+ * included (a split straight into the owning rank's memory).  That is not exercised by the tests: the test box has
+ * one GPU.  A tile is CC_SPLIT_TILE_ROWS consecutive rows (one workgroup; public so that tests can straddle it). */
+#define CC_SPLIT_TILE_ROWS 4096
+int  cc_split_device_bound(uint64_t n, uint32_t world, uint64_t* work_bytes);
+int  cc_split_batch_device(const cc_batch* d_in, uint64_t n, const uint8_t* d_rank_of_inst, uint32_t n_inst,
+                           uint32_t world, const cc_batch_out* outs, const uint64_t* out_cap, uint64_t* counts,
+                           uint64_t* const* d_rows, void* d_work, uint64_t work_bytes, void* stream);
+int  cc_merge_results_device(const uint32_t* d_inst, uint64_t n, const uint8_t* d_rank_of_inst, uint32_t n_inst,
+                             uint32_t world, const cc_results* parts, const cc_results* d_out, void* d_work,
+                             uint64_t work_bytes, void* stream);
+/* Measurement aid (scripts/split_rate.py), per calling thread, off by default.  With ms != NULL: ms[0..2] = the device
+ * times in milliseconds of the count kernel, the scan kernel and the scatter (or gather) kernel of this thread's last
+ * device split / merge call made while enabled (0 for a kernel the call did not launch), from events recorded around
+ * the launches; waits for that call's last kernel.  Then timing is switched on (enable != 0) or off for the calls that
+ * follow.  Enabled calls record five events on `stream`; nothing else about them changes. */
+int  cc_split_device_timing(int enable, float* ms);
+
 /* ---- the same decode on the GPU: wire bytes in, device columns out (copycat_amd/csrc/wire_plain.h, wire_gpu.hip) ----
  * These calls exist from this commit on, under the unchanged CC_ABI_VERSION 6 (symbols are only added).
  * A Copycat host holds the log's serialized entries, not columns.  cc_wire_decode_to_device takes the log segment
