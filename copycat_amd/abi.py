@@ -271,6 +271,14 @@ CC_WIRE_TILE_ROWS = 2048
 # the device split (include/copycat_apply.h "the same split and merge on the device"; copycat_amd/csrc/split_gpu.hip)
 CC_SPLIT_TILE_ROWS = 4096
 
+# the event merge (include/copycat_apply.h "the per-rank event streams back into log order"; csrc/evmerge.cpp,
+# evmerge_gpu.hip; the prototypes are in engine.lib()'s table, as every call's):
+#   cc_merge_events(parts, rows, row_counts, n, world, threads, out, total)
+#   cc_merge_events_device_bound(n, world, work_bytes)
+#   cc_merge_events_device(parts, d_rows, row_counts, n, world, d_out, total, d_work, work_bytes, stream)
+CC_EVMERGE_TILE_ROWS = 4096
+CC_EVMERGE_WINDOW_EVENTS = 1024
+
 
 class cc_wire_control(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("row", "kind", "key", "a", "b")]

@@ -11,8 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 
-ENGINE_SRCS = ["engine.hip", "apply_batch.hip", "map_big.hip", "partition.hip", "partition_ext.hip", "apply_value.hip", "value_path.hip", "apply_map.hip", "apply_map_hot.hip", "apply_coord.hip", "topic_fanout.hip", "events.hip", "quorum.hip", "close.hip", "map_wide.hip", "live.hip", "manager.hip", "retained.hip", "host_path.hip", "prefix_scan.hip", "map_small.hip", "map_cv.hip", "map_clear.hip", "wire.cpp", "split.cpp", "pack.cpp", "unpack.hip", "respack.cpp", "respack.hip", "evpack.cpp", "evpack.hip", "wire_gpu.hip", "split_gpu.hip"]
-ENGINE_HDRS = ["common.h", "engine_internal.h", "engine_state.h", "map_ops.h", "java_hashmap.h", "small_jhm.h", "jhm_tree.h", "big_jhm.h", "wire_plain.h", "pack_host.h", "pack_dev.h"]
+ENGINE_SRCS = ["engine.hip", "apply_batch.hip", "map_big.hip", "partition.hip", "partition_ext.hip", "apply_value.hip", "value_path.hip", "apply_map.hip", "apply_map_hot.hip", "apply_coord.hip", "topic_fanout.hip", "events.hip", "quorum.hip", "close.hip", "map_wide.hip", "live.hip", "manager.hip", "retained.hip", "host_path.hip", "prefix_scan.hip", "map_small.hip", "map_cv.hip", "map_clear.hip", "wire.cpp", "split.cpp", "pack.cpp", "unpack.hip", "respack.cpp", "respack.hip", "evpack.cpp", "evpack.hip", "wire_gpu.hip", "split_gpu.hip", "evmerge.cpp", "evmerge_gpu.hip"]
+ENGINE_HDRS = ["common.h", "engine_internal.h", "engine_state.h", "map_ops.h", "java_hashmap.h", "small_jhm.h", "jhm_tree.h", "big_jhm.h", "wire_plain.h", "pack_host.h", "pack_dev.h", "evmerge.h"]
 ENGINE_SO = os.path.join(HERE, "libcopycat_apply.so")
 WORKLOAD_SO = os.path.join(HERE, "libcopycat_workload.so")
 ARCH = os.environ.get("CC_OFFLOAD_ARCH", "gfx950")
@@ -35,7 +35,7 @@ def _run(cmd):
 
 # Units compiled with the compiler's kernel resource report: kept beside the object file (<unit>.resources.txt), and a
 # kernel of theirs that uses scratch fails the build (these kernels have no engine self-check in front of them).
-REPORT_SRCS = ("split_gpu.hip",)
+REPORT_SRCS = ("split_gpu.hip", "evmerge_gpu.hip")
 
 
 def _compile_unit(hipcc, flags, src, obj):
@@ -59,7 +59,7 @@ def _compile_engine(out_path, objdir, defines=()):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall"] + [f"-D{d}" for d in defines]
     os.makedirs(objdir, exist_ok=True)
-    objs = [os.path.join(objdir, f + ".o") for f in ENGINE_SRCS]  # (respack.cpp and respack.hip, evpack.cpp and evpack.hip: the whole name)
+    objs = [os.path.join(objdir, f + ".o") for f in ENGINE_SRCS]  # (respack.cpp and respack.hip, evpack.cpp and evpack.hip, evmerge: the whole name)
     jobs = max(1, min(len(ENGINE_SRCS), int(os.environ.get("MAX_JOBS", os.cpu_count() or 1)), 16))
     with ThreadPoolExecutor(jobs) as ex:
         list(ex.map(lambda so: _compile_unit(hipcc, flags, so[0], so[1]), zip(ENGINE_SRCS, objs)))

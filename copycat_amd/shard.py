@@ -219,6 +219,87 @@ def merge_by_owner_device(inst, own_dev, world, parts, stream=None):
     return status, value
 
 
+# ---- the per-rank event streams back into log order (cc_merge_events, evmerge.cpp / evmerge_gpu.hip) ----------------
+_EVENT_NP = {"u4": np.uint32, "u1": np.uint8, "u8": np.uint64}
+
+
+def merge_events(parts, rows, n, threads=0):
+    """parts[r] = rank r's events as numpy columns (pos, target, code, src, tag, payload: DeviceEvents.host()), pos a
+    row of the rank's share; rows[r] = the rank's log rows (split_batch's row ids) -> the one log-ordered stream as
+    the same dict, pos = the log row (cc_merge_events).  Streams of session closes or advance_time are refused."""
+    from .engine import _check, _np, lib
+
+    world = len(parts)
+    pr = (abi.cc_events * world)()
+    rowp = (C.c_void_p * world)()
+    row_counts = np.zeros(world, np.uint64)
+    keep = []
+    total = 0
+    for r, (p, rw) in enumerate(zip(parts, rows)):
+        cols = [np.ascontiguousarray(p[name], _EVENT_NP[dt]) for name, dt in abi.EVENT_COLUMNS]
+        cnt = np.array([len(cols[0])], np.uint64)
+        rw = np.ascontiguousarray(rw if rw is not None else [], np.uint64)
+        keep.append((cols, cnt, rw))
+        for (name, _), c in zip(abi.EVENT_COLUMNS, cols):
+            setattr(pr[r], name, _np(c) if len(c) else None)
+        pr[r].capacity, pr[r].count = len(cols[0]), _np(cnt)
+        rowp[r] = _np(rw) if len(rw) else None
+        row_counts[r] = len(rw)
+        total += len(cols[0])
+    out = {name: np.empty(total, _EVENT_NP[dt]) for name, dt in abi.EVENT_COLUMNS}
+    ocnt = np.zeros(1, np.uint64)
+    o = abi.cc_events(*[_np(out[name]) if total else None for name, _ in abi.EVENT_COLUMNS], total, _np(ocnt))
+    tot = C.c_uint64()
+    _check(lib().cc_merge_events(pr, rowp, _np(row_counts), n, world, _threads(threads), C.byref(o), C.byref(tot)))
+    out["count"] = int(tot.value)
+    return out
+
+
+def _events_workspace(n, world, device):
+    import torch
+
+    from .engine import _check, lib
+
+    need = C.c_uint64()
+    _check(lib().cc_merge_events_device_bound(n, world, C.byref(need)))
+    return torch.empty(need.value, dtype=torch.uint8, device=device)
+
+
+def merge_events_device(parts, rows, n, capacity=None, stream=None):
+    """parts[r] = rank r's DeviceEvents after apply_events on its share; rows[r] = the rank's log rows (the uint64
+    device tensors of split_batch_device(..., rows=True)) -> a DeviceEvents holding the one log-ordered stream, pos =
+    the log row (cc_merge_events_device), which Engine.events_to_host_packed accepts.  capacity: the output's rows
+    (default: the sum of the parts' capacities).  The output is complete on return (the stream is synchronised)."""
+    import torch
+
+    from .engine import DeviceEvents, _check, _np, _stream_ptr, lib
+
+    world = len(parts)
+    dev = parts[0].count.device
+    st = _stream_on(stream, dev)
+    work = _events_workspace(n, world, dev)
+    pr = (abi.cc_events * world)()
+    rowp = (C.c_void_p * world)()
+    row_counts = np.zeros(world, np.uint64)
+    for r, (p, rw) in enumerate(zip(parts, rows)):
+        pr[r] = p.struct()
+        if rw is not None and (rw.dtype != torch.uint64 or not rw.is_contiguous()):
+            raise ValueError("rows must be contiguous uint64 device tensors")
+        c = rw.numel() if rw is not None else 0
+        rowp[r] = rw.data_ptr() if c else None
+        row_counts[r] = c
+    cap = int(capacity) if capacity is not None else sum(int(p.capacity) for p in parts)
+    with torch.cuda.stream(st):
+        out = DeviceEvents(max(cap, 1), device=dev)
+    out.capacity = cap
+    o = out.struct()
+    tot = C.c_uint64()
+    _check(lib().cc_merge_events_device(pr, rowp, _np(row_counts), n, world, C.byref(o), C.byref(tot), work.data_ptr(),
+                                        work.numel(), _stream_ptr(st)))
+    st.synchronize()
+    return out
+
+
 def merge_results(n, parts):
     """parts: [(rows, status, value)] -> (status[n], value[n]) in log order."""
     status = np.zeros(n, np.uint8)

@@ -679,6 +679,74 @@ int  cc_merge_results_device(const uint32_t* d_inst, uint64_t n, const uint8_t* 
  * follow.  Enabled calls record five events on `stream`; nothing else about them changes. */
 int  cc_split_device_timing(int enable, float* ms);
 
+/* ---- the per-rank event streams back into log order (copycat_amd/csrc/evmerge.cpp, evmerge_gpu.hip) -----------------
+ * These calls exist from this commit on, under the unchanged CC_ABI_VERSION 6 (symbols are only added).
+ * Each rank's engine publishes its events with `pos` = a row of that rank's share.  cc_merge_events turns the `world`
+ * streams into the one log-ordered stream a single engine applying the whole log would have published (for a log that
+ * arms no timers: a rank's timers fire on its own rows' log time).  Host memory only, no engine.
+ * Inputs:
+ *   - parts[r]: rank r's event stream as an engine leaves it after cc_apply_batch* on its share (host columns, host
+ *     count).  A NULL count pointer means no events; a part's columns may be NULL when its count is 0.
+ *   - rows[r][p]: the log row of rank r's row p: the `rows` output of cc_split_batch, strictly increasing, every value
+ *     < n, no value shared by two ranks.  rows[r] may be NULL when part r has no events.
+ *   - row_counts[r]: the split's counts[r] (rows of rank r); n: rows of the log.
+ * Output:
+ *   - `out` holds all events ordered by log row; the events of one row keep the order their rank published them in.
+ *   - out->pos is the log row; target, code, src, tag and payload are copied.
+ *   - *out->count (when count is non-NULL) and *total take the number of events.  Rows of `out` past the total are
+ *     not touched.
+ *   - A log row belongs to exactly one rank, so there are no ties across ranks: the result is fully determined by the
+ *     inputs (and so is the failure reported when several events break a precondition: the lowest rank's first).
+ * Preconditions, checked; a failure returns CC_ERR_INVALID, cc_last_error names the rank and the event, and nothing is
+ * written to `out` (all validation completes before the first store):
+ *   - A part's pos is non-decreasing.  Every batch apply produces this: commit events are appended in batch-row order
+ *     (events.hip compacts the rows' event slots by an exclusive scan over the rows), a fan-out (topic publish, bus
+ *     broadcast, group member list) writes its run at its publishing row's place in that scan, and a timer that fires
+ *     during a batch publishes at the row whose log time fired it.
+ *   - Every pos < row_counts[r].  The streams of cc_sessions_close / cc_sessions_expire / cc_advance_time_events carry
+ *     pos = 0xFFFFFFFF: they are not batch events, belong to no log row, and are refused by this check.
+ *   - Every rows[r][pos] < n (the index is checked before it addresses `rows`, the value before it addresses anything).
+ *   - world in [1, 256]; n < 2^32; row_counts[r] <= n; every part's count, and the total, < 2^32.
+ *   - Two runs of events that map to the same log row (a `rows` that is not the split's) are refused where they are
+ *     seen: always by the host call, by the device call whenever the per-row runs do not add up to the events.  Neither
+ *     form reads or writes out of bounds on such input.
+ * Capacity; either case returns CC_ERR_CAPACITY with *total = the sum of the parts' counts and nothing written:
+ *   - a part whose count exceeds its own capacity (that rank's apply had overflowed); this is checked first;
+ *   - total > out->capacity; this is checked last, after the preconditions.
+ * n == 0: CC_OK with *total = 0, the parts are not read (the host call stores *out->count = 0, the device call makes no
+ * HIP call and stores nothing).  threads: worker threads (0 = hardware concurrency).
+ *
+ * cc_merge_events_device is the same call for streams in HBM, byte for byte:
+ *   - parts[r] and d_out are host structs whose column pointers AND count point to device memory, as an engine takes
+ *     them; d_rows is a host array of device pointers (cc_split_batch_device's d_rows); row_counts and total are host
+ *     memory.  The parts' counts are read on the device.
+ *   - No engine is involved; the call runs on the device that owns `stream` (the current device for the null stream).
+ *   - d_work: caller-owned device scratch, 16-byte aligned, of at least cc_merge_events_device_bound(n, world) bytes
+ *     (host arithmetic, no HIP call).  A smaller work_bytes, a NULL workspace, a NULL parts / d_rows / row_counts /
+ *     d_out / total, or a column that lacks its natural alignment (pos, target: 4; payload, count, d_rows[r]: 8) is
+ *     CC_ERR_INVALID before the first HIP call.  When every part's count pointer is NULL the call returns CC_OK with
+ *     *total = 0 before the first HIP call, too.
+ *   - It waits on the host exactly once, for the `world` counts, the total and the error word.  On CC_OK the gather is
+ *     enqueued on `stream` and NOT waited for (with total == 0: only the store of *d_out->count); the inputs and d_work
+ *     must stay untouched until the stream has passed them.  On any error nothing has been written to d_out.
+ *   - Inputs, outputs and the workspace must not overlap.
+ *   - Peer memory: d_out's columns may be any memory the device can store to, another GPU's peer-mapped HBM included.
+ *     That is not exercised by the tests: the test box has one GPU.
+ * A tile is CC_EVMERGE_TILE_ROWS consecutive log rows (one workgroup of the gather), whose events are moved
+ * CC_EVMERGE_WINDOW_EVENTS at a time; both are public so that tests can straddle them. */
+#define CC_EVMERGE_TILE_ROWS 4096
+#define CC_EVMERGE_WINDOW_EVENTS 1024
+int  cc_merge_events(const cc_events* parts, const uint64_t* const* rows, const uint64_t* row_counts, uint64_t n,
+                     uint32_t world, uint32_t threads, const cc_events* out, uint64_t* total);
+int  cc_merge_events_device_bound(uint64_t n, uint32_t world, uint64_t* work_bytes);
+int  cc_merge_events_device(const cc_events* parts, uint64_t* const* d_rows, const uint64_t* row_counts, uint64_t n,
+                            uint32_t world, const cc_events* d_out, uint64_t* total, void* d_work, uint64_t work_bytes,
+                            void* stream);
+/* Measurement aid (scripts/evmerge_rate.py), per calling thread, off by default, as cc_split_device_timing: ms[0..3] =
+ * the device times in milliseconds of the workspace clear, the mark kernel, the two scan kernels and the gather of
+ * this thread's last cc_merge_events_device call made while enabled (0 for a step the call did not reach). */
+int  cc_merge_events_device_timing(int enable, float* ms);
+
 /* ---- the same decode on the GPU: wire bytes in, device columns out (copycat_amd/csrc/wire_plain.h, wire_gpu.hip) ----
  * These calls exist from this commit on, under the unchanged CC_ABI_VERSION 6 (symbols are only added).
  * A Copycat host holds the log's serialized entries, not columns.  cc_wire_decode_to_device takes the log segment
