@@ -850,6 +850,7 @@ int Batch::sub_value(Sub& s) {
   va.st_ab = e->d_st_ab;
   va.tiles = s.v3 ? (uint32_t)((s.hi - s.lo + kV3Tile - 1) / kV3Tile) : s.tiles;
   va.v3 = s.v3;
+  va.rst_word = e->d_rst_word;
   va.ca = c->a;
   va.cb = c->b;
   va.lo = s.lo;
@@ -1141,7 +1142,7 @@ int Batch::unpermute(Sub& s) {
   ua.dummy_status = e->d_rst_status + e->sub_batch;
   ua.dummy_value = e->d_rst_value + e->sub_batch;
   ua.v3 = s.v3;
-  ua.words = reinterpret_cast<const uint64_t*>(e->d_st_ab);
+  ua.words = e->d_rst_word;
   ua.mark = marker_of(e);
   s.unpermuted = true;
   return launched(launch_unpermute(ua, st), "unpermute launch", st);

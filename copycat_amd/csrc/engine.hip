@@ -104,7 +104,7 @@ static void free_all(cc_engine* e) {
                   e->d_cvset,    e->d_cvcnt,    e->d_cvev_key, e->d_cvev_key2, e->d_cvev_val, e->d_cvev_val2, e->d_cvev_ctl,
                   e->d_cvseg,    e->d_cvtemp,   e->d_clrq,    e->d_clrq_n,   e->d_clr_keys,   e->d_clr_keys2, e->d_clr_off,
                   e->d_clr_base, e->d_clr_eend, e->d_clr_temp, e->d_tbl_ep, e->d_clr_scan, e->d_clr_stemp, e->d_clr_btab, e->d_cvbloom,
-                  e->d_px,       e->d_px_bcnt,  e->d_px_evn,   e->d_fan};
+                  e->d_px,       e->d_px_bcnt,  e->d_px_evn,   e->d_fan,       e->d_rst_word};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void*& p : e->hw_buf)
@@ -341,6 +341,7 @@ extern "C" int cc_engine_create(const cc_config* cfg, cc_engine** out) {
   }
   ALLOC(e->d_rst_status, e->sub_batch + 4 * kPT);  // + dummy rows for unconditional result stores
   ALLOC(e->d_rst_value, sizeof(uint64_t) * (e->sub_batch + 4 * kPT));
+  ALLOC(e->d_rst_word, sizeof(uint32_t) * (e->sub_batch + 4 * kPT));  // value_path.hip's packed result words
   ALLOC(e->d_err, sizeof(uint32_t));
   {
     hipError_t x = hipHostMalloc((void**)&e->h_pin, 8 * sizeof(uint64_t), hipHostMallocDefault);

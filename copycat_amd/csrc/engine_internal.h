@@ -82,7 +82,7 @@ size_t part_ext_chunk(uint32_t sb, bool maps, bool ids);  // k_part_ext's chunk 
 
 struct ValueArgs {
   const uint32_t* st_meta;
-  u64x2* st_ab;  // (value_path.hip: the records, then the packed results over them)
+  u64x2* st_ab;  // (value_path.hip: the 8-byte records, read only)
   const uint16_t* ttab;
   uint32_t tiles;
   uint32_t sb;           // total super-buckets (ttab row width - 1)
@@ -95,6 +95,7 @@ struct ValueArgs {
   uint64_t dummy;        // first of the dummy result rows after the staging area (= sub_batch)
   uint32_t* err;
   bool v3;               // value_path.hip: 8-byte records, 8192-commit tiles
+  uint32_t* rst_word;    //   the packed 4-byte result words [sub_batch + dummy rows] (escaped payloads in rst_value)
   const uint64_t* ca;    //   the batch's a / b columns (operands of escaped records) and the sub-batch's first row
   const uint64_t* cb;
   uint64_t lo;
@@ -705,12 +706,12 @@ struct UnpermuteArgs {
   uint64_t* out_value;
   uint8_t* dummy_status;  // 4 x kPT dummy result rows (after the staging area) for unconditional stores
   uint64_t* dummy_value;
-  bool v3;                // value_path.hip tiles (8192 commits): packed result words in `words` (the records' area)
-  const uint64_t* words;
+  bool v3;                // value_path.hip tiles (8192 commits): packed 4-byte result words in `words`
+  const uint32_t* words;
   Marker mark;
 };
 int launch_unpermute(const UnpermuteArgs& a, hipStream_t st);
-int launch_unpermute_v3(const UnpermuteArgs& a, const uint64_t* words, hipStream_t st);
+int launch_unpermute_v3(const UnpermuteArgs& a, const uint32_t* words, hipStream_t st);
 
 // The bulk compaction view (retained.hip, cc_retained_bitmap): bit (i - first) of bitmap set iff log index i is held
 // by a state machine without clean().

@@ -193,6 +193,7 @@ struct cc_engine {
   uint16_t* d_ttab = nullptr;
   uint8_t* d_rst_status = nullptr;
   uint64_t* d_rst_value = nullptr;
+  uint32_t* d_rst_word = nullptr;  // value-only engines: the packed 4-byte result words (value_path.hip), sized like d_rst_value
   uint32_t* d_err = nullptr;
   // pinned host words for the per-batch / per-sub-batch counter readbacks: a copy into pageable memory returns only
   // after its own round trip, so two counters read back cost two idle gaps of ~200 us on the GPU

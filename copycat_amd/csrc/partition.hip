@@ -170,7 +170,7 @@ int launch_unpermute(const UnpermuteArgs& a, hipStream_t st) {
   const uint64_t tiles = (n + kTile - 1) / kTile;
   if (tiles == 0) return 0;
   a.mark(K_UNPERMUTE, 1, st);
-  if (a.v3) {  // value_path.hip: packed result words over the records (k_unpermute_v3)
+  if (a.v3) {  // value_path.hip: packed 4-byte result words (k_unpermute_v3)
     if (launch_unpermute_v3(a, a.words, st)) return -1;
   } else {
     const uint32_t grid = (uint32_t)(tiles < kPersistGrid ? tiles : kPersistGrid);

@@ -139,13 +139,33 @@ __device__ inline void v3_decode_escaped(uint64_t r, const uint64_t* __restrict_
 }
 
 // ---- the packed result ----------------------------------------------------------------------------------------
-// The apply writes each result over its record: payload (56-bit two's complement) | status (7 bits: code | tag << 4,
-// tags <= 6) << 56 | escaped << 63.  A payload that does not fit (escaped) is written whole to rst_value at the
-// same staging position, where the unpermute reads it.  (9 B per commit in two arrays before: a status byte array
-// whose lines were written in ~32-byte pieces by different workgroups, and the value array.)
-constexpr int kV3ResBits = 56;
-__device__ inline uint64_t v3_pack_result(uint32_t status, uint64_t v, bool esc) {
-  return (esc ? (1ull << 63) : (v & ((1ull << kV3ResBits) - 1))) | ((uint64_t)(status & 0x7Fu) << kV3ResBits);
+// The apply writes one 4-byte word per result into an array of its own (rst_word, indexed by staging position like
+// the records):
+//   bits 0..23   the payload as a 24-bit two's complement number (sign-extended back by the unpermute); 0 if escaped
+//   bits 24..30  the status, 7 bits: code | tag << 4 (tags <= 6)
+//   bit 31       escaped: the payload is outside [-2^23, 2^23) and is written whole to rst_value at the same staging
+//                position, where the unpermute reads it
+// The word follows the record's idea (32-bit expected value, 14-bit delta): a CAS answers a boolean, a get /
+// getAndSet of a DistributedAtomicLong a small counter, so a 56-bit payload laid over the 8-byte record moved 4 bytes
+// per commit twice (the apply's write, the unpermute's read) that almost never carried anything.  (9 B per commit in
+// two arrays before round 3: a status byte array whose lines were written in ~32-byte pieces by different workgroups,
+// and the value array.)
+constexpr int kV3ResBits = 24;
+__device__ inline bool v3_res_fits(uint64_t v) {  // v == sign-extension of its low 24 bits
+  return (uint64_t)(int64_t)((int32_t)((uint32_t)v << (32 - kV3ResBits)) >> (32 - kV3ResBits)) == v;
+}
+__device__ inline uint32_t v3_pack_result(uint32_t status, uint64_t v, bool esc) {
+  return (esc ? (1u << 31) : ((uint32_t)v & ((1u << kV3ResBits) - 1))) | ((status & 0x7Fu) << kV3ResBits);
+}
+__device__ inline uint64_t v3_result_payload(uint32_t wd) {
+  return (uint64_t)(int64_t)((int32_t)(wd << (32 - kV3ResBits)) >> (32 - kV3ResBits));
+}
+// Element i of a staging array through a 32-bit byte offset (uniform base + zero-extended offset: no 64-bit shift
+// and add per access).  Staging positions, the dummy rows' among them, stay below 2^29 (launch_apply_value_v3).
+template <class T>
+__device__ inline T* v3_at(T* base, uint32_t i) {
+  using B = std::conditional_t<std::is_const<T>::value, const char, char>;
+  return reinterpret_cast<T*>(reinterpret_cast<B*>(base) + (uint32_t)(i * (uint32_t)sizeof(T)));
 }
 
 // ---- k_part_v4: one persistent 1024-thread workgroup per CU, one pass per 8192-commit tile --------------------
@@ -552,7 +572,8 @@ __device__ inline void v3_loader_wait(uint32_t* ctr, uint32_t target) {
 }
 
 template <int NS>
-__global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(uint64_t* __restrict__ st_rec,
+__global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(const uint64_t* __restrict__ st_rec,
+                                                        uint32_t* __restrict__ rst_word,
                                                         const uint64_t* __restrict__ ca, const uint64_t* __restrict__ cb,
                                                         uint64_t lo, const uint16_t* __restrict__ ttab, uint32_t tiles,
                                                         uint32_t sb, uint32_t* __restrict__ val_meta,
@@ -688,7 +709,7 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
     }                                                                                             \
     if (diag & 2u) gpos = c < cnt ? c : dpos; /* diagnostics: contiguous positions (wrong results) */ \
     g##J = gpos;                                                                                  \
-    rr##J = st_rec[gpos];                                                                         \
+    rr##J = *v3_at(st_rec, gpos);                                                                 \
   }
 #define CC_LOAD_CHUNK(C0)                                                                         \
   {                                                                                               \
@@ -711,22 +732,22 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
   // the registers' chunk as ranked at the end of the iteration before: rank (< 3072) | slot << 16
   uint32_t rs0 = 0, rs1 = 0, rs2 = 0, rs3 = 0;
   // the results of the chunk walked before (buffer b, positions qp / gq) into registers, ahead of the placement that
-  // overwrites them; then over the records themselves at their staging positions (each record is read once, by this
-  // workgroup, a chunk earlier): one packed word per result (v3_pack_result), unconditional stores (rows past the
-  // end go to the dummy words).  A value that does not fit the word also goes to rst_value: looked for once per
-  // wave and group, so the common path has no per-lane branch.
+  // overwrites them; then into rst_word at the records' staging positions: one packed 4-byte word per result
+  // (v3_pack_result), unconditional stores (rows past the end go to the dummy words).  A value that does not fit the
+  // word's 24 bits also goes to rst_value: looked for once per wave and group, so the common path has no per-lane
+  // branch.
 #define CC_RES_READ(J) const u64x2 re##J = sab[b][qp##J];
 #define CC_RES_WRITE(J)                                                             \
   {                                                                                 \
-    const bool esc_ = !v3_fits(re##J.x, kV3ResBits) && gq##J < dpos0;               \
-    uint64_t wd_ = v3_pack_result((uint32_t)re##J.y, re##J.x, false);               \
+    const bool esc_ = !v3_res_fits(re##J.x) && gq##J < dpos0;                       \
+    uint32_t wd_ = v3_pack_result((uint32_t)re##J.y, re##J.x, false);               \
     if (__ballot(esc_)) { /* wave-uniform, rare */                                  \
       if (esc_) {                                                                   \
         wd_ = v3_pack_result((uint32_t)re##J.y, re##J.x, true);                     \
-        rst_value[gq##J] = re##J.x;                                                 \
+        *v3_at(rst_value, gq##J) = re##J.x;                                         \
       }                                                                             \
     }                                                                               \
-    st_rec[gq##J] = wd_;                                                            \
+    *v3_at(rst_word, gq##J) = wd_;                                                  \
   }
   // Rank the registers' chunk into this wave's counter row (the last thing a loader wave does before a workgroup
   // barrier: the barrier, not a counter, orders the twelve rows before the scan that follows it).
@@ -915,89 +936,103 @@ __global__ __launch_bounds__(V3A<NS>::T, V3A<NS>::MINW) void k_apply_value_v3(ui
 }
 
 // ---- k_unpermute_v3: the packed results back to log order ----------------------------------------------------
-// partition.hip k_unpermute over packed result words: per 8192-commit tile (persistent, two 512-thread workgroups per
-// CU), the tile's staged words are read contiguously into LDS (the next tile's are loaded into registers meanwhile),
-// then each thread writes 4-row groups in log order through cpos: status bytes as one u32, values as two 16-byte
-// stores.  Unknown-session rows (cpos 0xFFFF) get UNKNOWN_SESSION here (ResourceManager.java:60-69).
+// partition.hip k_unpermute over packed 4-byte result words: per 8192-commit tile (persistent, two 512-thread
+// workgroups per CU), the tile's staged words are read contiguously into a 32 KB LDS image (the next tile's are loaded
+// into registers meanwhile: 4 sixteen-byte loads of words and 4 eight-byte loads of cpos per thread), then the
+// results are gathered through cpos and written in log order.  Unknown-session rows (cpos 0xFFFF) get
+// UNKNOWN_SESSION here (ResourceManager.java:60-69).  6 B read and 9 B written per commit.
+//
+// The stores are whole lines: a wave's cpos load covers 256 commits, four a lane; the lanes trade them (two shuffles
+// per half) so that lane l writes commits 2l, 2l+1 of each half of 128 -- a value store of the wave is 1 KB contiguous
+// and a status store one 128-byte line -- and the stores are nontemporal: the outputs are written once and no kernel
+// of this pipeline reads them, so they need not stay in the caches the staging arrays are read from (a cache policy
+// only: a later reader, the result encoder or a copy, sees them like any other store).  Measured on c2 (ms per
+// step of this kernel, two runs each): four commits a lane (16-byte value stores at a 32-byte stride) 0.277-0.283;
+// the same nontemporal 0.340 (half-written lines no longer meet in L2); whole lines 0.270; whole lines nontemporal
+// 0.241.  Workgroups per CU, before the stores changed: two 0.276, three 0.280, four (64 VGPRs: 44 B of scratch)
+// 0.333.
 constexpr int kU3T = 512;
+constexpr int kU3Wg = 2;  // workgroups per CU the grid is sized for
+typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
 template <int NT, int TL>
 __global__ __launch_bounds__(NT) void k_unpermute_v3(const uint16_t* __restrict__ cpos, uint32_t tiles, uint64_t n,
-                                                   const uint64_t* __restrict__ words, const uint64_t* __restrict__ esc_value,
+                                                   const uint32_t* __restrict__ words, const uint64_t* __restrict__ esc_value,
                                                    uint8_t* __restrict__ out_status, uint64_t* __restrict__ out_value,
                                                    uint8_t* __restrict__ dummy_status, uint64_t* __restrict__ dummy_value) {
-  constexpr int kUnVal = TL / (2 * NT);  // 16-byte word-pair loads per thread per tile (8)
+  constexpr int kUnVal = TL / (4 * NT);  // 16-byte four-word loads per thread per tile (4)
   constexpr int kUnPos = TL / (4 * NT);  // 4-commit cpos groups per thread per tile (4)
-  static_assert(kUnVal == 8 && kUnPos == 4, "unpermute prefetch registers");
-  __shared__ uint4 lw2[TL / 2];
-  const uint64_t* lw = reinterpret_cast<const uint64_t*>(lw2);
-  const uint32_t t = threadIdx.x;
+  static_assert(kUnVal == 4 && kUnPos == 4, "unpermute prefetch registers");
+  __shared__ uint4 lw4[TL / 4];
+  const uint32_t* lw = reinterpret_cast<const uint32_t*>(lw4);
+  const uint32_t t = threadIdx.x, l = t & 63u;
   // prefetch registers as named scalars (an array would live in scratch and make every prefetch wait)
-  uint4 v0, v1, v2, v3, v4, v5, v6, v7;
+  uint4 v0, v1, v2, v3;
   uint2 p0, p1, p2, p3;
   auto load = [&](uint32_t TT) {
     const uint64_t i0 = (uint64_t)TT * TL;
     const uint4* sv = reinterpret_cast<const uint4*>(words + i0) + t;
     const uint2* sp = reinterpret_cast<const uint2*>(cpos + i0) + t;
     v0 = sv[0 * NT]; v1 = sv[1 * NT]; v2 = sv[2 * NT]; v3 = sv[3 * NT];
-    v4 = sv[4 * NT]; v5 = sv[5 * NT]; v6 = sv[6 * NT]; v7 = sv[7 * NT];
     p0 = sp[0 * NT]; p1 = sp[1 * NT]; p2 = sp[2 * NT]; p3 = sp[3 * NT];
   };
   uint32_t T = blockIdx.x;
   load(T < tiles ? T : tiles - 1);
   const uint8_t unk = CC_STATUS(CC_ST_UNKNOWN_SESSION, CC_TAG_NULL);
-  uint64_t tail_i = ~0ull, tail_v0 = 0, tail_v1 = 0, tail_v2 = 0;
+  uint64_t tail_i = ~0ull, tail_v = 0;
   uint32_t tail_sw = 0;
   for (; T < tiles; T += gridDim.x) {
     lds_barrier();  // the previous tile's scatter is done reading LDS
-    lw2[t + 0 * NT] = v0; lw2[t + 1 * NT] = v1; lw2[t + 2 * NT] = v2; lw2[t + 3 * NT] = v3;
-    lw2[t + 4 * NT] = v4; lw2[t + 5 * NT] = v5; lw2[t + 6 * NT] = v6; lw2[t + 7 * NT] = v7;
+    lw4[t + 0 * NT] = v0; lw4[t + 1 * NT] = v1; lw4[t + 2 * NT] = v2; lw4[t + 3 * NT] = v3;
     const uint2 pp[kUnPos] = {p0, p1, p2, p3};
     lds_barrier();
     load(T + gridDim.x < tiles ? T + gridDim.x : tiles - 1);
     const uint64_t i0 = (uint64_t)T * TL;
 #pragma unroll
     for (int k = 0; k < kUnPos; ++k) {
-      const uint64_t i = i0 + 4 * (uint64_t)(t + k * NT);  // commits i .. i+3
-      const uint32_t p[4] = {pp[k].x & 0xFFFF, pp[k].x >> 16, pp[k].y & 0xFFFF, pp[k].y >> 16};
-      uint32_t sw = 0;
-      uint64_t v[4];
+      // lane j holds the cpos of commits w0 + 4j .. 4j+3 (w0: the wave's first commit of this group); lane l takes
+      // commits w0 + 128h + 2l, +1: one half of lane 32h + l/2's four
+      const uint64_t w0 = i0 + 4 * (uint64_t)(t - l + k * NT);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const bool ok = p[q] != 0xFFFF;
-        const uint64_t wd = ok ? lw[p[q]] : 0;
-        uint64_t x = (uint64_t)(((int64_t)(wd << (64 - kV3ResBits))) >> (64 - kV3ResBits));
-        if (wd >> 63) x = esc_value[i0 + p[q]];  // escaped payload (rare)
-        sw |= (uint32_t)(ok ? (uint32_t)(wd >> kV3ResBits) & 0x7Fu : unk) << (8 * q);
-        v[q] = x;
-      }
-      const bool in = i + 4 <= n;
-      uint32_t* os = in ? reinterpret_cast<uint32_t*>(out_status) + i / 4 : reinterpret_cast<uint32_t*>(dummy_status) + t;
-      u64x2* ov = in ? reinterpret_cast<u64x2*>(out_value) + i / 2 : reinterpret_cast<u64x2*>(dummy_value) + 2 * t;
-      *os = sw;
-      ov[0] = u64x2{v[0], v[1]};
-      ov[1] = u64x2{v[2], v[3]};
-      if (!in && i < n) {  // the straddling group (at most one in the grid): written after the loop
-        tail_sw = sw;
-        tail_v0 = v[0];
-        tail_v1 = v[1];
-        tail_v2 = v[2];
-        tail_i = i;
+      for (int h = 0; h < 2; ++h) {
+        const int src = 32 * h + (int)(l >> 1);
+        const uint32_t px = (uint32_t)__shfl((int)pp[k].x, src, 64), py = (uint32_t)__shfl((int)pp[k].y, src, 64);
+        const uint32_t pr = (l & 1u) ? py : px;
+        const uint32_t p[2] = {pr & 0xFFFF, pr >> 16};
+        const uint64_t i = w0 + 128 * h + 2 * l;  // commits i, i+1
+        uint32_t sw = 0;
+        uint64_t v[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const bool ok = p[q] != 0xFFFF;
+          const uint32_t wd = ok ? lw[p[q]] : 0;
+          uint64_t x = v3_result_payload(wd);
+          if (wd >> 31) x = esc_value[i0 + p[q]];  // escaped payload (rare)
+          sw |= (uint32_t)(ok ? (wd >> kV3ResBits) & 0x7Fu : unk) << (8 * q);
+          v[q] = x;
+        }
+        const bool in = i + 2 <= n;
+        uint16_t* os = in ? reinterpret_cast<uint16_t*>(out_status) + i / 2 : reinterpret_cast<uint16_t*>(dummy_status) + t;
+        ull2* ov = in ? reinterpret_cast<ull2*>(out_value) + i / 2 : reinterpret_cast<ull2*>(dummy_value) + t;
+        __builtin_nontemporal_store((uint16_t)sw, os);
+        __builtin_nontemporal_store(ull2{v[0], v[1]}, ov);
+        if (!in && i < n) {  // the straddling pair (at most one in the grid): its first commit, written after the loop
+          tail_sw = sw;
+          tail_v = v[0];
+          tail_i = i;
+        }
       }
     }
   }
-  if (tail_i != ~0ull) {  // commits tail_i .. n-1 (1 to 3 of them)
-    const uint64_t vv[3] = {tail_v0, tail_v1, tail_v2};
-    for (int q = 0; q < 3 && tail_i + q < n; ++q) {
-      out_status[tail_i + q] = (uint8_t)(tail_sw >> (8 * q));
-      out_value[tail_i + q] = vv[q];
-    }
+  if (tail_i != ~0ull) {  // commit n-1 of an odd n
+    out_status[tail_i] = (uint8_t)tail_sw;
+    out_value[tail_i] = tail_v;
   }
 }
 
-int launch_unpermute_v3(const UnpermuteArgs& a, const uint64_t* words, hipStream_t st) {
+int launch_unpermute_v3(const UnpermuteArgs& a, const uint32_t* words, hipStream_t st) {
   const uint64_t n = a.hi - a.lo;
   const uint64_t t3 = (n + kV3Tile - 1) / kV3Tile;
-  const uint32_t grid = (uint32_t)(t3 < 2 * kPersistGrid ? t3 : 2 * kPersistGrid);
+  const uint32_t grid = (uint32_t)(t3 < (uint64_t)kU3Wg * kPersistGrid ? t3 : (uint64_t)kU3Wg * kPersistGrid);
   hipLaunchKernelGGL((k_unpermute_v3<kU3T, kV3Tile>), dim3(grid), dim3(kU3T), 0, st, a.cpos, (uint32_t)t3, n, words,
                      a.rst_value, a.out_status + a.lo, a.out_value + a.lo, a.dummy_status, a.dummy_value);
   return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -1021,10 +1056,10 @@ int launch_part_v3(const PartArgs& a, uint32_t tiles, hipStream_t st) {
 }
 
 int launch_apply_value_v3(const ValueArgs& a, hipStream_t st) {
-  // (the kernel keeps staging positions, the dummy words' among them, in 32 bits)
-  if (a.tiles > (uint32_t)kV3MaxTiles || a.dummy + V3A<256>::T > 0xFFFFFFFFull) return -1;
+  // (the kernel keeps staging positions, the dummy words' among them, in 32 bits, and their byte offsets too: v3_at)
+  if (a.tiles > (uint32_t)kV3MaxTiles || a.dummy + V3A<256>::T > (1ull << 29)) return -1;
   hipLaunchKernelGGL(k_apply_value_v3<256>, dim3(a.sb_val), dim3(V3A<256>::T), 0, st,
-                     reinterpret_cast<uint64_t*>(a.st_ab), a.ca, a.cb, a.lo, a.ttab, a.tiles, a.sb, a.val_meta, a.val_v,
+                     reinterpret_cast<const uint64_t*>(a.st_ab), a.rst_word, a.ca, a.cb, a.lo, a.ttab, a.tiles, a.sb, a.val_meta, a.val_v,
                      a.rst_value, a.dummy, a.err);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
