@@ -369,6 +369,18 @@ class cc_evpack_block(C.Structure):
     _fields_ = [("rows", C.c_uint32), ("bytes", C.c_uint32), ("offset", C.c_uint64), ("col", cc_pack_col * 6)]
 
 
+# packed blobs both ways on the device (include/copycat_apply.h: cc_pack_from_device under "packed host batches",
+# cc_respack_to_device under "packed result blobs", cc_evpack_to_device under "packed event blobs"; csrc/pack_enc.hip,
+# unpack_res.hip).  name -> (result, arguments); engine.lib() binds them with the rest of its table.
+PACK_DEVICE_PROTOTYPES = {
+    # (e, d_cols, n, h_blob, cap, bytes, stream)
+    "cc_pack_from_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    # (e, h_blob, bytes, d_out, stream)
+    "cc_respack_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "cc_evpack_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+}
+
+
 class cc_packed_opts(C.Structure):
     _fields_ = [
         ("chunk_rows", C.c_uint64),

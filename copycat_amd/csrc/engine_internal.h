@@ -788,6 +788,47 @@ struct EvpackArgs {
 };
 int launch_evpack(const EvpackArgs& a, hipStream_t st);
 
+// Wide batch columns -> the directory and data areas of a batch blob (pack_enc.hip): block k of `dir` encodes rows
+// [4096 k, ...) of the columns `present` names, in cc_batch order (each 16-byte aligned; the others are not read).
+// `data` takes the blob's bytes from blob offset `data_base` (a multiple of 16) on, with room for the worst case
+// (every present column raw + 144); *total = the data bytes written.
+struct PackEncArgs {
+  const void* col[9];
+  uint32_t present;
+  uint64_t n;
+  cc_pack_block* dir;
+  uint8_t* data;
+  uint64_t data_base;
+  unsigned long long* total;
+};
+int launch_pack_enc(const PackEncArgs& a, hipStream_t st);
+
+// A result blob / an event blob -> the wide columns (unpack_res.hip): block k of `dir` decodes into rows [4096 k, ...)
+// of the columns (each 16-byte aligned).  `data` holds the blob's bytes from blob offset `data_base` on; both are device
+// copies of a blob that passed cc_respack_check / cc_evpack_check.  Events: *count = n, written by the kernel.
+struct ResUnpackArgs {
+  const cc_respack_block* dir;
+  const uint8_t* data;
+  uint64_t data_base;
+  uint8_t* status;
+  uint64_t* value;
+};
+int launch_res_unpack(const ResUnpackArgs& a, uint32_t blocks, hipStream_t st);
+struct EvUnpackArgs {
+  const cc_evpack_block* dir;
+  const uint8_t* data;
+  uint64_t data_base;
+  uint32_t* pos;
+  uint32_t* target;
+  uint8_t* code;
+  uint8_t* src;
+  uint8_t* tag;
+  uint64_t* payload;
+  uint64_t* count;
+  uint64_t n;
+};
+int launch_ev_unpack(const EvUnpackArgs& a, uint32_t blocks, hipStream_t st);
+
 // Wire bytes -> wide columns (wire_gpu.hip k_wire_decode): tile k decodes entries [CC_WIRE_TILE_ROWS k, ...) of the
 // staged segment.  Entry i is bytes[off[i] - off[0], off[i + 1] - off[0]); `bytes` is 16-byte aligned and padded so
 // that whole 16-byte loads up to the segment's rounded-up end stay inside it.  Plain entries (wire_plain.h) are

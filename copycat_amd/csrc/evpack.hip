@@ -108,17 +108,6 @@ __global__ __launch_bounds__(256) void k_evpack_place(EvpackArgs a, uint32_t blo
   place_blocks(a.dir, blocks, a.data_base, a.total);
 }
 
-__device__ inline void write_u32(uint8_t* lds, const cc_pack_col& c, const uint32_t* v, uint32_t rows, uint8_t* area) {
-  const uint32_t w = uni((uint32_t)c.width);
-  if (w == 0) return;
-  uint8_t* const out = area + uni(c.offset);
-  if (w == 4) return copy_raw((const uint8_t*)v, out, rows * 4);
-  const uint32_t base = uni((uint32_t)c.base), bytes = r16(rows * w);
-  if (w == 1) enc32<1>(lds, v, base, rows, bytes);
-  else enc32<2>(lds, v, base, rows, bytes);
-  flush(lds, out, bytes);
-}
-
 __global__ __launch_bounds__(256) void k_evpack_write(EvpackArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[kRows * 8];
   const cc_evpack_block& b = a.dir[blockIdx.x];

@@ -1693,6 +1693,132 @@ extern "C" int cc_retained_bitmap_host(cc_engine* e, uint64_t first, uint64_t co
   return CC_OK;
 }
 
+// ---- packed blobs both ways on the device (pack_enc.hip, unpack_res.hip) ------------------------------------------------
+// For a host that holds a log in HBM and splits it there (cc_split_batch_device): a share leaves as a batch blob
+// (cc_pack_from_device), and the ranks' result and event blobs come back as device columns (cc_respack_to_device,
+// cc_evpack_to_device) for cc_merge_results_device / cc_merge_events_device.  The encoder's staging is
+// {total word (16 B) | directory entries | data areas}, as the result encoder's; the decoders stage the blob where
+// cc_unpack_to_device does (kHwBlob0: the engine is synchronised between two such calls anyway).
+namespace {
+
+enum ShSlot : int { kHwShare = kWsSlots, kShSlots };
+static_assert(kShSlots <= 32, "cc_engine::hw_buf");
+
+// a validated result or event blob copied into the engine's staging on `st`; *d = the device copy
+int blob_to_staging(cc_engine* e, const void* h_blob, const cc_pack_header* hd, hipStream_t st, const uint8_t** d) {
+  void* p = nullptr;
+  TRY(hw(e, kHwBlob0, hd->bytes, &p));
+  HIPCHECK(hipMemcpyAsync(p, h_blob, hd->bytes, hipMemcpyHostToDevice, st));
+  *d = (const uint8_t*)p;
+  return CC_OK;
+}
+
+}  // namespace
+
+extern "C" int cc_pack_from_device(cc_engine* e, const cc_batch* d_cols, uint64_t n, void* h_blob, uint64_t cap,
+                                   uint64_t* bytes, void* stream) {
+  if (!e || !d_cols || !bytes || (cap && !h_blob)) return set_err(CC_ERR_INVALID, "pack from device: null argument");
+  if ((uintptr_t)h_blob & 15) return set_err(CC_ERR_INVALID, "pack from device: the blob must be 16-byte aligned");
+  const void* const col[9] = {d_cols->index, d_cols->time, d_cols->inst, d_cols->op, d_cols->flags,
+                              d_cols->key,   d_cols->a,    d_cols->b,    d_cols->aux};
+  uint32_t present = 0;
+  for (int c = 0; c < 9; ++c) {
+    if ((uintptr_t)col[c] & 15)
+      return set_err(CC_ERR_INVALID, "pack from device: a present column's device pointer is not 16-byte aligned");
+    if (col[c]) present |= 1u << c;
+  }
+  uint64_t bound = 0;
+  TRY(cc_pack_bound(n, present, &bound));
+  if (cap < bound) {
+    *bytes = bound;
+    return set_err(CC_ERR_CAPACITY, "pack from device: the blob buffer is smaller than cc_pack_bound (*bytes = the bound)");
+  }
+  cc_pack_header hd{};
+  hd.magic = (uint32_t)CC_PACK_MAGIC;
+  hd.version = CC_PACK_VERSION;
+  hd.n = n;
+  hd.blocks = rp_blocks(n);
+  hd.bytes = sizeof hd;
+  hd.present = present;
+  hd.block_rows = CC_PACK_BLOCK_ROWS;
+  if (n) {
+    if (hd.blocks > 0x7FFFFFFFull) return set_err(CC_ERR_CAPACITY, "pack from device: more than 2^31 blocks");
+    HIPCHECK(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (!e->rp_pin) HIPCHECK(hipHostMalloc((void**)&e->rp_pin, 16, hipHostMallocDefault));
+    const uint64_t db = hd.blocks * sizeof(cc_pack_block);
+    const uint64_t room = bound - sizeof hd - db;  // every present column raw; the tail block's paddings
+    void* p = nullptr;
+    TRY(hw(e, kHwShare, kRpHead + db + room, &p));
+    PackEncArgs a{};
+    for (int c = 0; c < 9; ++c) a.col[c] = col[c];
+    a.present = present, a.n = n;
+    a.dir = (cc_pack_block*)((uint8_t*)p + kRpHead);
+    a.data = (uint8_t*)p + kRpHead + db;
+    a.data_base = sizeof hd + db;
+    a.total = (unsigned long long*)p;
+    if (launch_pack_enc(a, st)) return set_err(CC_ERR_HIP, "batch blob encode launch", hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(e->rp_pin, p, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    const uint64_t total = *e->rp_pin;
+    if (total > room) return set_err(CC_ERR_STATE, "internal check: the batch blob encoder wrote past its bound");
+    // directory and data are adjacent in the staging as they are in the blob: one copy
+    HIPCHECK(hipMemcpyAsync((uint8_t*)h_blob + sizeof hd, (uint8_t*)p + kRpHead, db + total, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    hd.bytes += db + total;
+  }
+  std::memcpy(h_blob, &hd, sizeof hd);
+  *bytes = hd.bytes;
+  return CC_OK;
+}
+
+extern "C" int cc_respack_to_device(cc_engine* e, const void* h_blob, uint64_t bytes, const cc_results* d_out, void* stream) {
+  if (!e || !d_out) return set_err(CC_ERR_INVALID, "result blob to device: null argument");
+  uint64_t n = 0;
+  TRY(cc_respack_check(h_blob, bytes, &n));  // (a malformed blob never reaches the GPU)
+  if (n == 0) return CC_OK;
+  if (!d_out->status || !d_out->value || (((uintptr_t)d_out->status | (uintptr_t)d_out->value) & 15))
+    return set_err(CC_ERR_INVALID, "result blob to device: status and value device pointers must be non-null and 16-byte aligned");
+  const cc_pack_header* hd = (const cc_pack_header*)h_blob;
+  if (hd->blocks > 0x7FFFFFFFull) return set_err(CC_ERR_CAPACITY, "result blob to device: more than 2^31 blocks");
+  HIPCHECK(hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  const uint8_t* d = nullptr;
+  TRY(blob_to_staging(e, h_blob, hd, st, &d));
+  ResUnpackArgs a{};
+  a.dir = (const cc_respack_block*)(d + sizeof *hd), a.data = d, a.data_base = 0;
+  a.status = d_out->status, a.value = d_out->value;
+  if (launch_res_unpack(a, (uint32_t)hd->blocks, st)) return set_err(CC_ERR_HIP, "result blob decode launch", hipGetLastError());
+  return CC_OK;
+}
+
+extern "C" int cc_evpack_to_device(cc_engine* e, const void* h_blob, uint64_t bytes, const cc_events* d_out, void* stream) {
+  if (!e || !d_out || !d_out->count) return set_err(CC_ERR_INVALID, "event blob to device: null argument");
+  uint64_t n = 0;
+  TRY(cc_evpack_check(h_blob, bytes, &n));  // (a malformed blob never reaches the GPU)
+  if (d_out->capacity < n) return set_err(CC_ERR_CAPACITY, "event blob to device: more events than d_out->capacity");
+  HIPCHECK(hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) {
+    HIPCHECK(hipMemsetAsync(d_out->count, 0, sizeof(uint64_t), st));
+    return CC_OK;
+  }
+  if (!d_out->pos || !d_out->target || !d_out->code || !d_out->src || !d_out->tag || !d_out->payload ||
+      (((uintptr_t)d_out->pos | (uintptr_t)d_out->target | (uintptr_t)d_out->code | (uintptr_t)d_out->src |
+        (uintptr_t)d_out->tag | (uintptr_t)d_out->payload) & 15))
+    return set_err(CC_ERR_INVALID, "event blob to device: the six device columns must be non-null and 16-byte aligned");
+  const cc_pack_header* hd = (const cc_pack_header*)h_blob;
+  if (hd->blocks > 0x7FFFFFFFull) return set_err(CC_ERR_CAPACITY, "event blob to device: more than 2^31 blocks");
+  const uint8_t* d = nullptr;
+  TRY(blob_to_staging(e, h_blob, hd, st, &d));
+  EvUnpackArgs a{};
+  a.dir = (const cc_evpack_block*)(d + sizeof *hd), a.data = d, a.data_base = 0;
+  a.pos = d_out->pos, a.target = d_out->target, a.code = d_out->code, a.src = d_out->src, a.tag = d_out->tag;
+  a.payload = d_out->payload, a.count = d_out->count, a.n = n;
+  if (launch_ev_unpack(a, (uint32_t)hd->blocks, st)) return set_err(CC_ERR_HIP, "event blob decode launch", hipGetLastError());
+  return CC_OK;
+}
+
 // ---- plain device memory (for the stateless device calls and hosts that keep columns resident) ---------------
 extern "C" int cc_device_alloc(int device, uint64_t bytes, void** d_out) {
   if (!d_out) return set_err(CC_ERR_INVALID, "null argument");

@@ -151,6 +151,7 @@ def lib():
             "cc_apply_wire_host_packed": (i32, [P, P, P, P, P, u64, P, P, u64, u64, P, P, P, P, P, P]),
             "cc_wire_packed_timeline": (i32, [P, u64, P, P]),
         }
+        sig.update(abi.PACK_DEVICE_PROTOTYPES)
         for name, (res, args) in sig.items():
             f = getattr(L, name)
             f.restype = res
@@ -676,6 +677,42 @@ class Engine:
             t = cols.get(name)
             setattr(s, name, t.data_ptr() if t is not None else None)
         _check(self.L.cc_unpack_to_device(self.h, blob.ctypes.data, blob.nbytes, C.byref(s), _stream_ptr(stream)))
+
+    def batch_to_host_packed(self, db, stream=None, out=None):
+        """cc_pack_from_device: device batch columns (a DeviceBatch; an absent column is left out of the blob) -> a packed
+        batch blob in host memory, byte for byte batch.pack of the same columns: what apply_host_packed* and
+        unpack_to_device take.  Synchronous.  `out`: a 16-byte-aligned uint8 buffer of at least batch.pack_bound bytes
+        for the present columns."""
+        from .batch import _aligned_bytes
+
+        s = db.struct()
+        present = sum(1 << k for k, (name, _) in enumerate(abi.BATCH_COLUMNS) if db.cols.get(name) is not None)
+        blob = out
+        if blob is None:
+            bound = C.c_uint64()
+            _check(self.L.cc_pack_bound(db.n, present, C.byref(bound)))
+            blob = _aligned_bytes(bound.value)
+        size = C.c_uint64()
+        _check(self.L.cc_pack_from_device(self.h, C.byref(s), db.n, blob.ctypes.data, blob.nbytes, C.byref(size),
+                                          _stream_ptr(stream)))
+        return blob[:size.value]
+
+    def results_to_device(self, blob, status, value, stream=None):
+        """cc_respack_to_device: a packed result blob in host memory -> the device tensors status (uint8) and value
+        (64-bit), results_info(blob)["n"] rows each, 16-byte aligned; byte for byte batch.unpack_results.  Stream-ordered
+        and not waited for: sync before `blob` or this engine is used again."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        r = abi.cc_results(status.data_ptr(), value.data_ptr())
+        _check(self.L.cc_respack_to_device(self.h, blob.ctypes.data, blob.nbytes, C.byref(r), _stream_ptr(stream)))
+
+    def events_to_device(self, blob, events, stream=None):
+        """cc_evpack_to_device: a packed event blob in host memory -> the device event stream `events` (DeviceEvents of
+        capacity >= the blob's events), its device count word included; byte for byte batch.unpack_events.  `events` is
+        then what merge_events_device and events_to_host_packed take.  Stream-ordered and not waited for: sync before
+        `blob` or this engine is used again."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        s = events.struct()
+        _check(self.L.cc_evpack_to_device(self.h, blob.ctypes.data, blob.nbytes, C.byref(s), _stream_ptr(stream)))
 
     def sync(self):
         _check(self.L.cc_sync(self.h))

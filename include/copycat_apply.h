@@ -918,6 +918,19 @@ int  cc_unpack_batch(const void* h_blob, uint64_t bytes, const cc_batch_out* h_o
  * blob never reaches the GPU. */
 int  cc_unpack_to_device(cc_engine* e, const void* h_blob, uint64_t bytes, const cc_batch_out* d_cols, void* stream);
 
+/* The encoder on the device: device columns (d_cols: a host struct of device pointers, NULL column = absent, every
+ * present one 16-byte aligned, n rows) -> a batch blob in the caller's host memory (h_blob 16-byte aligned), for a host
+ * whose columns are already in HBM (cc_wire_decode_to_device, cc_unpack_to_device, a share of cc_split_batch_device)
+ * and must leave it narrow.  The call exists from this commit on, under the unchanged CC_ABI_VERSION 6.  A gfx950
+ * encoder (pack_enc.hip) builds the blob in engine-owned staging on `stream`; only header + directory + used data bytes
+ * are copied.  Synchronous: on return the stream is drained and the blob is final, byte for byte cc_pack_batch's for the
+ * same columns at any thread count (reserved words and absent columns' entries 0, areas back to back in block order,
+ * the paddings zero), so every consumer of a batch blob takes it.  A misaligned column or blob: CC_ERR_INVALID;
+ * cap < cc_pack_bound(n, present): CC_ERR_CAPACITY with *bytes = the bound, before any launch.  n == 0: a header-only
+ * blob, as cc_pack_batch. */
+int  cc_pack_from_device(cc_engine* e, const cc_batch* d_cols, uint64_t n, void* h_blob, uint64_t cap, uint64_t* bytes,
+                         void* stream);
+
 typedef struct cc_packed_opts {
   uint64_t chunk_rows;  /* rows per pipeline chunk; 0 = 16 Mi; rounded up to whole blocks, capped by max_batch and the
                            engine's extended sub-batch */
@@ -1007,6 +1020,16 @@ int  cc_respack_unpack(const void* h_blob, uint64_t bytes, const cc_results* h_o
 int  cc_respack_from_device(cc_engine* e, const cc_results* d_results, uint64_t n, void* h_blob, uint64_t cap,
                             uint64_t* bytes, void* stream);
 
+/* The decoder on the device (exists from this commit on, under the unchanged CC_ABI_VERSION 6): copy a result blob in
+ * host memory to the device and decode it into the caller's device columns (d_out: status and value in HBM, header.n
+ * rows each, 16-byte aligned), e.g. a rank's answer on its way into cc_merge_results_device.  The counterpart of
+ * cc_unpack_to_device, with its staging and stream rules: stream-ordered on `stream` and not waited for; the blob is
+ * copied into the engine-owned buffer cc_unpack_to_device uses, which the next such call on this engine reuses: sync
+ * before the host blob or that engine is used again.  cc_respack_check runs first: a malformed blob is CC_ERR_INVALID
+ * and never reaches the GPU.  The decoded columns are cc_respack_unpack's byte for byte (unpack_res.hip).  A
+ * header-only blob writes nothing. */
+int  cc_respack_to_device(cc_engine* e, const void* h_blob, uint64_t bytes, const cc_results* d_out, void* stream);
+
 /* cc_apply_batch_host_packed with the result rows replaced by a result blob: the same chunking, streams, checkpoint /
  * rollback and event-stream rules; state, events, applied index and *h_rows_done are exactly those of
  * cc_apply_batch_host_packed on the same input.  Per chunk the encoder runs on the engine's stream after the apply,
@@ -1093,6 +1116,16 @@ int  cc_evpack_unpack(const void* h_blob, uint64_t bytes, const cc_events* h_out
  * *bytes = the bound, before any launch.  Zero events: a header-only blob. */
 int  cc_evpack_from_device(cc_engine* e, const cc_events* d_events, void* h_blob, uint64_t cap_bytes, uint64_t* bytes,
                            uint64_t* count, void* stream);
+
+/* The decoder on the device (exists from this commit on, under the unchanged CC_ABI_VERSION 6): copy an event blob in
+ * host memory to the device and decode it into a device event stream (d_out: six device columns, each 16-byte aligned,
+ * and the device count word), with cc_respack_to_device's staging and stream rules (stream-ordered, not waited for;
+ * sync before the host blob or the engine is used again).  cc_evpack_check runs first: a malformed blob is
+ * CC_ERR_INVALID and never reaches the GPU; d_out->capacity < header.n: CC_ERR_CAPACITY, nothing copied or launched.
+ * The decoded columns are cc_evpack_unpack's byte for byte, a CC_PK_BY_POS payload included (unpack_res.hip), and the
+ * DEVICE word *d_out->count is set to header.n on the stream: d_out is then an event stream cc_merge_events_device
+ * and cc_evpack_from_device take as it stands.  A header-only blob writes no column and sets the count to 0. */
+int  cc_evpack_to_device(cc_engine* e, const void* h_blob, uint64_t bytes, const cc_events* d_out, void* stream);
 
 /* cc_apply_batch_host_packed_results with the host event stream replaced by an event blob of at most ev_capacity
  * events.  State, result blob, applied index, *h_rows_done and the return code are exactly those of that call made with
