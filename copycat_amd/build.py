@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 
 ENGINE_SRCS = ["engine.hip", "apply_batch.hip", "map_big.hip", "partition.hip", "partition_ext.hip", "apply_value.hip", "value_path.hip", "apply_map.hip", "apply_map_hot.hip", "apply_coord.hip", "topic_fanout.hip", "events.hip", "quorum.hip", "close.hip", "map_wide.hip", "live.hip", "manager.hip", "retained.hip", "host_path.hip", "prefix_scan.hip", "map_small.hip", "map_cv.hip", "map_clear.hip", "wire.cpp", "split.cpp", "pack.cpp", "unpack.hip", "respack.cpp", "respack.hip", "evpack.cpp", "evpack.hip", "wire_gpu.hip", "split_gpu.hip", "evmerge.cpp", "evmerge_gpu.hip", "pack_enc.hip", "unpack_res.hip"]
-ENGINE_HDRS = ["common.h", "engine_internal.h", "engine_state.h", "map_ops.h", "java_hashmap.h", "small_jhm.h", "jhm_tree.h", "big_jhm.h", "wire_plain.h", "pack_host.h", "pack_dev.h", "evmerge.h"]
+ENGINE_HDRS = ["common.h", "engine_internal.h", "engine_state.h", "map_ops.h", "java_hashmap.h", "small_jhm.h", "jhm_tree.h", "big_jhm.h", "wire_plain.h", "pack_host.h", "pack_dev.h", "evmerge.h", "value_group.h"]
 ENGINE_SO = os.path.join(HERE, "libcopycat_apply.so")
 WORKLOAD_SO = os.path.join(HERE, "libcopycat_workload.so")
 ARCH = os.environ.get("CC_OFFLOAD_ARCH", "gfx950")

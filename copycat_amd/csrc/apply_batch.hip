@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "engine_state.h"
+#include "value_group.h"
 
 using namespace cc;
 
@@ -298,6 +299,8 @@ struct Sub {
   uint32_t cv_n = 0;
   bool clr_on = false;  // clears in the stream in this batch (map_clear.hip)
   bool v3 = false;      // value-only engines: value_path.hip
+  bool vg = false;      // [lo, hi) is a group staged in the engine's group arrays (value_group.h): the partition
+  uint64_t vg_seg = 0;  // covers all of it, sub_value and unpermute its segment vg_seg
   ClrSubArgs ca{};
   ClrCtx cctx{};
   CvSubArgs cva{};
@@ -341,6 +344,8 @@ struct Batch {
   HotArgs hot_args(uint64_t lo, uint64_t hi) const;  // what the hot-key detect and bind share
   Next next_action() const;
   int cut_sub(uint64_t lo, uint64_t seg_hi, Sub& s), apply_sub(Sub& s);
+  bool group_staged(uint64_t rows);             // value-only: the group staging holds (a group of) this stretch
+  int apply_group(uint64_t lo, uint64_t& hi);   // value-only: one group from lo, cut before hi
   int sub_clear_epochs(Sub& s), sub_hot_bind(Sub& s), sub_partition(Sub& s), sub_value(Sub& s), sub_cv_prepare(Sub& s);
   int sub_map(Sub& s), sub_ttl_tail(Sub& s), sub_size_tail(Sub& s), sub_small_replay(Sub& s, uint32_t events);
   int sub_coord(Sub& s), unpermute(Sub& s), sub_answers(Sub& s), sub_events(Sub& s);
@@ -830,6 +835,12 @@ int Batch::sub_partition(Sub& s) {
   pa.cpos = e->d_cpos;
   pa.ttab = e->d_ttab;
   pa.dummy = e->sub_batch;
+  if (s.vg) {  // the whole group in one launch: tile-local records, cpos and ttab rows in the group arrays
+    pa.st_ab = reinterpret_cast<u64x2*>(e->d_vg_rec);
+    pa.cpos = e->d_vg_cpos;
+    pa.ttab = e->d_vg_ttab;
+    pa.dummy = e->vg_rows;
+  }
   pa.v3 = s.v3;
   pa.mark = marker_of(e);
   if (launch_partition(pa, st)) {
@@ -858,6 +869,22 @@ int Batch::sub_value(Sub& s) {
   va.val_meta = e->d_val_meta;
   va.val_v = e->d_val_v;
   va.dummy = e->sub_batch;
+  if (s.vg) {
+    // Segment vg_seg of the group: the group arrays from the segment's first tile on, its first row, and the dummy
+    // position counted from that tile.  Rows and staging move together: an escaped record finds its operands at row
+    // lo + its tile's first position (value_path.hip v3_decode_escaped), both counted from the segment's start.
+    VgSegment g;
+    const int rc = vg_segment(s.hi - s.lo, e->sub_batch, e->vg_rows, s.vg_seg, g);
+    if (rc) return set_err(rc, "value group: a segment outside its staging");
+    const uint64_t p0 = g.tile0 * kV3Tile;
+    va.st_ab = reinterpret_cast<u64x2*>(e->d_vg_rec + p0);
+    va.rst_word = e->d_vg_word + p0;
+    va.rst_value = e->d_vg_value + p0;
+    va.ttab = e->d_vg_ttab + g.tile0 * (va.sb + 1);
+    va.tiles = (uint32_t)g.tiles;
+    va.lo = s.lo + g.row0;
+    va.dummy = g.dummy;
+  }
   return launched(launch_apply_value(va, st), "apply launch", st);
 }
 
@@ -1143,6 +1170,21 @@ int Batch::unpermute(Sub& s) {
   ua.dummy_value = e->d_rst_value + e->sub_batch;
   ua.v3 = s.v3;
   ua.words = e->d_rst_word;
+  if (s.vg) {
+    // Segment vg_seg of the group, right behind its apply, whose result words are then still in the last-level cache
+    // (one unpermute over a whole 100M-row group read them from HBM and took 0.07 ms per step longer than the
+    // launches it saved: DESIGN 4.3).  The status dummy rows stay the per-sub-batch array's.
+    VgSegment g;
+    const int rc = vg_segment(s.hi - s.lo, e->sub_batch, e->vg_rows, s.vg_seg, g);
+    if (rc) return set_err(rc, "value group: a segment outside its staging");
+    const uint64_t p0 = g.tile0 * kV3Tile;
+    ua.lo = s.lo + g.row0;
+    ua.hi = ua.lo + g.rows;
+    ua.cpos = e->d_vg_cpos + p0;
+    ua.rst_value = e->d_vg_value + p0;
+    ua.dummy_value = e->d_vg_value + e->vg_rows;
+    ua.words = e->d_vg_word + p0;
+  }
   ua.mark = marker_of(e);
   s.unpermuted = true;
   return launched(launch_unpermute(ua, st), "unpermute launch", st);
@@ -1242,6 +1284,58 @@ int Batch::apply_sub(Sub& s) {
   if (!s.unpermuted) TRY(unpermute(s));
   TRY(sub_answers(s));
   if (e->coord_on) TRY(sub_events(s));
+  return CC_OK;
+}
+
+// ---- a value-only engine's group (value_group.h) ----
+
+// The group staging for a stretch of `rows` rows: allocated by the first stretch longer than a sub-batch, for
+// min(rows, max_batch, the group's limit) in whole tiles; grown by a longer one; kept until destroy.  false: the
+// per-sub-batch path takes the stretch (one segment, CC_VALUE_GROUP_TILES=0, or the allocation failed).
+bool Batch::group_staged(uint64_t rows) {
+  VgPlan p;
+  if (e->ext || rows <= e->sub_batch || !vg_plan(rows, e->sub_batch, e->cfg.max_batch, e->vg_knob, p) || !p.group_rows)
+    return false;
+  if (p.staging_rows <= e->vg_rows) return true;
+  if (p.staging_rows >= e->vg_refused) return false;
+  const uint64_t rows_al = p.staging_rows, pad = 4 * kPT;
+  const int rc = regrow({BUF(e->d_vg_rec, sizeof(uint64_t) * (rows_al + pad)), BUF(e->d_vg_cpos, sizeof(uint16_t) * rows_al),
+                         BUF(e->d_vg_ttab, sizeof(uint16_t) * (rows_al / kV3Tile) * (e->sb_total() + 1)),
+                         BUF(e->d_vg_word, sizeof(uint32_t) * (rows_al + pad)),
+                         BUF(e->d_vg_value, sizeof(uint64_t) * (rows_al + pad))},
+                        e->vg_rows, rows_al, "hipMalloc value group staging");
+  if (rc) {  // (not an error of the call: the launches below check hipGetLastError, so the failure is taken off it)
+    (void)hipGetLastError();
+    e->vg_refused = rows_al;
+    return false;
+  }
+  return true;
+}
+
+// One group from lo: the partition over all of it in one launch, then the apply and the unpermute segment by segment
+// in log order (the walker state goes from one apply launch to the next through val_meta / val_v).
+int Batch::apply_group(uint64_t lo, uint64_t& hi) {
+  // what else cuts a sub-batch (cut_sub: a map's 128th clear, containsValue rows, the index span, the event-buffer
+  // swap) needs maps; a value-only engine has none
+  if (e->ext || e->map_bits || e->coord_on || e->ttl_live || e->span_cut || e->sm_alt_on || e->clr_n ||
+      !e->clr_heavy.empty() || !e->isc_rows.empty())
+    return set_err(CC_ERR_STATE, "value group on an engine whose sub-batches have other cuts");
+  VgPlan p;
+  if (!vg_plan(hi - lo, e->sub_batch, e->cfg.max_batch, e->vg_knob, p) || !p.group_rows)
+    return set_err(CC_ERR_STATE, "value group without a plan");
+  hi = std::min(hi, lo + std::min(p.group_rows, e->vg_rows));
+  Sub g;
+  g.lo = lo;
+  g.hi = hi;
+  g.tiles = (uint32_t)((hi - lo + kTile - 1) / kTile);
+  g.v3 = g.vg = true;
+  TRY(sub_partition(g));
+  const uint64_t segs = vg_segments(hi - lo, e->sub_batch);
+  for (g.vg_seg = 0; g.vg_seg < segs; ++g.vg_seg) {
+    ++e->stat_subbatches;
+    TRY(sub_value(g));
+    TRY(unpermute(g));
+  }
   return CC_OK;
 }
 
@@ -1396,6 +1490,12 @@ extern "C" int cc_apply_batch(cc_engine* e, const cc_batch* c, uint64_t n, const
   for (;;) {
     const Next nx = b.next_action();
     for (uint64_t lo = b.cur; lo < nx.hi;) {
+      if (b.group_staged(nx.hi - lo)) {  // value-only, more than one segment: one partition and one unpermute
+        uint64_t hi = nx.hi;
+        TRY(b.apply_group(lo, hi));
+        lo = hi;
+        continue;
+      }
       Sub s;
       TRY(b.cut_sub(lo, nx.hi, s));
       TRY(b.apply_sub(s));

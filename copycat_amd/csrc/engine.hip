@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "engine_state.h"
+#include "value_group.h"
 
 using namespace cc;
 
@@ -104,7 +105,8 @@ static void free_all(cc_engine* e) {
                   e->d_cvset,    e->d_cvcnt,    e->d_cvev_key, e->d_cvev_key2, e->d_cvev_val, e->d_cvev_val2, e->d_cvev_ctl,
                   e->d_cvseg,    e->d_cvtemp,   e->d_clrq,    e->d_clrq_n,   e->d_clr_keys,   e->d_clr_keys2, e->d_clr_off,
                   e->d_clr_base, e->d_clr_eend, e->d_clr_temp, e->d_tbl_ep, e->d_clr_scan, e->d_clr_stemp, e->d_clr_btab, e->d_cvbloom,
-                  e->d_px,       e->d_px_bcnt,  e->d_px_evn,   e->d_fan,       e->d_rst_word};
+                  e->d_px,       e->d_px_bcnt,  e->d_px_evn,   e->d_fan,       e->d_rst_word,
+                  e->d_vg_rec,   e->d_vg_cpos,  e->d_vg_ttab,  e->d_vg_word,   e->d_vg_value};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (void*& p : e->hw_buf)
@@ -222,8 +224,13 @@ extern "C" int cc_engine_create(const cc_config* cfg, cc_engine** out) {
   const uint32_t ccap = cfg->coord_cap ? cfg->coord_cap : kCoordCapDefault;
   if (ccap < kCoordCapDefault || ccap > kCoordCapMax || (ccap & (ccap - 1)))
     return set_err(CC_ERR_INVALID, "coord_cap must be 0 or a power of two in [64, 65536]");
+  // CC_VALUE_GROUP_TILES, read per engine (value_group.h): one process can hold engines of both kinds
+  uint64_t vg_knob = kVgNoCap;
+  if (!vg_parse_knob(getenv("CC_VALUE_GROUP_TILES"), vg_knob))
+    return set_err(CC_ERR_INVALID, "CC_VALUE_GROUP_TILES must be a number of tiles (0: one partition per sub-batch)");
   cc_engine* e = new cc_engine();
   e->cfg = *cfg;
+  e->vg_knob = vg_knob;
   e->coord_cap = ccap;
   e->device = cfg->device;
   hipError_t he = hipSetDevice(e->device);
@@ -840,6 +847,29 @@ extern "C" int cc_engine_counters(cc_engine* e, uint64_t* out, uint32_t n) {
     for (uint32_t b = 0; b < kBigSlots; ++b) v[4] += own[b] != 0;
   }
   for (uint32_t i = 0; i < n && i < 5; ++i) out[i] = v[i];
+  return CC_OK;
+}
+
+// ---- the group / segment arithmetic of the value-only apply (value_group.h), as plain host calls ----
+extern "C" int cc_value_group_knob(const char* text, uint64_t* tiles) {
+  if (!tiles) return set_err(CC_ERR_INVALID, "null argument");
+  return vg_parse_knob(text, *tiles) ? CC_OK : set_err(CC_ERR_INVALID, "CC_VALUE_GROUP_TILES must be a number of tiles");
+}
+extern "C" int cc_value_group_plan(uint64_t n, uint64_t sub_batch, uint64_t max_batch, uint64_t knob_tiles, uint64_t* out) {
+  VgPlan p;
+  if (!out) return set_err(CC_ERR_INVALID, "null argument");
+  if (!vg_plan(n, sub_batch, max_batch, knob_tiles, p))
+    return set_err(CC_ERR_INVALID, "sub_batch must be whole value tiles, at most kV3MaxTiles of them");
+  out[0] = p.group_rows, out[1] = p.groups, out[2] = p.staging_rows;
+  return CC_OK;
+}
+extern "C" int cc_value_group_segment(uint64_t rows, uint64_t sub_batch, uint64_t staging_rows, uint64_t j, uint64_t* out) {
+  VgSegment s;
+  if (!out) return set_err(CC_ERR_INVALID, "null argument");
+  const int rc = vg_segment(rows, sub_batch, staging_rows, j, s);
+  if (rc) return set_err(rc, rc == CC_ERR_CAPACITY ? "the group does not fit its staging below 2^29 positions"
+                                                   : "no such segment, or sizes that are not whole value tiles");
+  out[0] = s.row0, out[1] = s.rows, out[2] = s.tile0, out[3] = s.tiles, out[4] = s.dummy;
   return CC_OK;
 }
 

@@ -194,6 +194,19 @@ struct cc_engine {
   uint8_t* d_rst_status = nullptr;
   uint64_t* d_rst_value = nullptr;
   uint32_t* d_rst_word = nullptr;  // value-only engines: the packed 4-byte result words (value_path.hip), sized like d_rst_value
+  // Group staging of a value-only engine (value_group.h): k_part_v4's records, cpos and ttab and the apply's result
+  // words and escaped payloads for a whole group, so that one partition launch and one unpermute launch cover it
+  // (22 B per position and the ttab rows; + dummy rows).  Allocated by the first value-only call longer than a
+  // sub-batch, grown by a longer one, freed at destroy; the arrays above stay as they are and serve the per-sub-batch
+  // path (calls of one sub-batch, CC_VALUE_GROUP_TILES=0, a failed allocation, the engine once it is ext).
+  uint64_t vg_knob = ~0ull;       // CC_VALUE_GROUP_TILES when the engine was created (value_group.h vg_parse_knob)
+  uint64_t vg_rows = 0;           // positions the arrays hold (whole tiles); the first dummy position of a group
+  uint64_t vg_refused = ~0ull;    // the smallest size whose allocation failed (not tried again at or above it)
+  uint64_t* d_vg_rec = nullptr;   // [vg_rows + 4 kPT]
+  uint16_t* d_vg_cpos = nullptr;  // [vg_rows]
+  uint16_t* d_vg_ttab = nullptr;  // [vg_rows / kV3Tile][sb + 1]
+  uint32_t* d_vg_word = nullptr;  // [vg_rows + 4 kPT]
+  uint64_t* d_vg_value = nullptr; // [vg_rows + 4 kPT]
   uint32_t* d_err = nullptr;
   // pinned host words for the per-batch / per-sub-batch counter readbacks: a copy into pageable memory returns only
   // after its own round trip, so two counters read back cost two idle gaps of ~200 us on the GPU

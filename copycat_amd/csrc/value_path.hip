@@ -1041,8 +1041,10 @@ int launch_unpermute_v3(const UnpermuteArgs& a, const uint32_t* words, hipStream
 // Slots per value super-bucket: 256.  (128-slot buckets -- two 512-thread apply workgroups per CU -- measured slower
 // on c2: apply 0.91 -> 0.98, partition 0.88 -> 0.92 ms/step, profiles/r03/ab_ns128: the apply is bound by the loaders'
 // instruction and LDS throughput, not by the latency a second workgroup would hide, and 16-record runs over-fetch.)
+// Any tile count the staging holds (a.dummy: its positions): a sub-batch, or a value-only engine's whole group.  The
+// kV3MaxTiles limit is the apply's run table's and is checked where it lives, launch_apply_value_v3.
 int launch_part_v3(const PartArgs& a, uint32_t tiles, hipStream_t st) {
-  if (a.sb > (uint32_t)kMaxSb || tiles > (uint32_t)kV3MaxTiles) return -1;
+  if (a.sb > (uint32_t)kMaxSb || (uint64_t)tiles * kV3Tile > a.dummy) return -1;
   const uint32_t grid = tiles < (uint32_t)kPersistGrid ? tiles : (uint32_t)kPersistGrid;
   const uint32_t kp = (a.sb + kWave - 1) / kWave;  // super-buckets per lane of the scan wave
 #define CC_LAUNCH4(KP)                                                                                                 \

@@ -152,7 +152,17 @@ def lib():
             "cc_wire_packed_timeline": (i32, [P, u64, P, P]),
         }
         sig.update(abi.PACK_DEVICE_PROTOTYPES)
+        # the value-only apply's group / segment arithmetic (host calls; a library picked through CC_ENGINE_SO for an
+        # A/B against an earlier commit may predate them)
+        value_group = {
+            "cc_value_group_knob": (i32, [C.c_char_p, P]),
+            "cc_value_group_plan": (i32, [u64, u64, u64, u64, P]),
+            "cc_value_group_segment": (i32, [u64, u64, u64, u64, P]),
+        }
+        sig.update(value_group)
         for name, (res, args) in sig.items():
+            if name in value_group and os.environ.get("CC_ENGINE_SO") and not hasattr(L, name):
+                continue
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args

@@ -381,6 +381,24 @@ int  cc_applied_index(cc_engine* e, uint64_t* out);
  * out[4] big HashMap models held now (maps past capacity 64 with a tree bin: map_big.hip; reading it syncs).
  * n = entries of `out` to fill (at most 5). */
 int  cc_engine_counters(cc_engine* e, uint64_t* out, uint32_t n);
+/* The group / segment arithmetic of the value-only apply (host arithmetic, no device needed; symbols added under the
+ * unchanged CC_ABI_VERSION 6).  A value-only call longer than a sub-batch is partitioned and unpermuted once per
+ * *group* and applied once per *segment* (= sub-batch) of the group.
+ *   cc_value_group_knob     the text of the environment variable CC_VALUE_GROUP_TILES (read when an engine is created):
+ *                           NULL / "" -> UINT64_MAX (groups as large as the kernels' 32-bit staging offsets allow:
+ *                           2^29 - 4096 positions, in whole segments), "0" -> 0 (one partition and one unpermute per
+ *                           sub-batch), "k" -> at most k tiles of 8192 rows per group, rounded down to whole segments
+ *                           (at least one); anything else CC_ERR_INVALID.
+ *   cc_value_group_plan     out[0] rows per group at most (0: the per-sub-batch path), out[1] groups a call of n rows
+ *                           runs, out[2] staging positions allocated for it (min(n, max_batch, out[0]) in whole tiles).
+ *   cc_value_group_segment  segment j of a group of `rows` rows staged in arrays of staging_rows positions: out[0] its
+ *                           first row (from the group's first), out[1] rows, out[2] first tile, out[3] tiles, out[4]
+ *                           its first dummy position counted from its first tile.  CC_ERR_CAPACITY when the group does
+ *                           not fit the staging or the dummy rows would pass 2^29 positions; CC_ERR_INVALID for j past
+ *                           the group's last segment. */
+int  cc_value_group_knob(const char* text, uint64_t* tiles);
+int  cc_value_group_plan(uint64_t n, uint64_t sub_batch, uint64_t max_batch, uint64_t knob_tiles, uint64_t* out /*[3]*/);
+int  cc_value_group_segment(uint64_t rows, uint64_t sub_batch, uint64_t staging_rows, uint64_t j, uint64_t* out /*[5]*/);
 /* The same watermark written stream-ordered into device memory (u64 at d_out) without a host sync: what a rank feeds
  * to the RCCL all-gather of applied watermarks after each batch. */
 int  cc_applied_index_async(cc_engine* e, uint64_t* d_out, void* stream);
