@@ -279,6 +279,20 @@ CC_SPLIT_TILE_ROWS = 4096
 CC_EVMERGE_TILE_ROWS = 4096
 CC_EVMERGE_WINDOW_EVENTS = 1024
 
+# the route (include/copycat_apply.h "an event stream to its client sessions"; csrc/route.cpp, route_gpu.hip):
+#   cc_route_events(in, n_events, session_of_inst, id_of_inst, n_inst, n_sessions, threads, out, out_instance, dir,
+#                   n_active)
+#   cc_route_events_device_bound(n_events, n_sessions, work_bytes)
+#   cc_route_events_device(d_in, n_events, d_session_of_inst, d_id_of_inst, n_inst, n_sessions, d_out, d_out_instance,
+#                          d_dir, n_active, d_work, work_bytes, stream)
+CC_ROUTE_DIGIT_BITS = 8
+CC_ROUTE_TILE_EVENTS = 4096
+CC_ROUTE_TIMING_SLOTS = 6
+
+
+class cc_route_dir(C.Structure):
+    _fields_ = [("session", C.c_void_p), ("start", C.c_void_p), ("capacity", C.c_uint64), ("count", C.c_void_p)]
+
 
 class cc_wire_control(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("row", "kind", "key", "a", "b")]

@@ -125,6 +125,10 @@ def lib():
             "cc_merge_events_device_bound": (i32, [u64, u32, P]),
             "cc_merge_events_device": (i32, [P, P, P, u64, u32, P, P, P, u64, P]),
             "cc_merge_events_device_timing": (i32, [i32, P]),
+            "cc_route_events": (i32, [P, u64, P, P, u32, u32, u32, P, P, P, P]),
+            "cc_route_events_device_bound": (i32, [u64, u32, P]),
+            "cc_route_events_device": (i32, [P, u64, P, P, u32, u32, P, P, P, P, P, u64, P]),
+            "cc_route_events_device_timing": (i32, [i32, P]),
             "cc_pack_bound": (i32, [u64, u32, P]),
             "cc_pack_batch": (i32, [P, u64, P, u64, u32, P]),
             "cc_pack_check": (i32, [P, u64, P, P]),

@@ -765,6 +765,87 @@ int  cc_merge_events_device(const cc_events* parts, uint64_t* const* d_rows, con
  * this thread's last cc_merge_events_device call made while enabled (0 for a step the call did not reach). */
 int  cc_merge_events_device_timing(int enable, float* ms);
 
+/* ---- an event stream to its client sessions (copycat_amd/csrc/route.cpp, route_gpu.hip) ------------------------------
+ * These calls exist from this commit on, under the unchanged CC_ABI_VERSION 6 (symbols are only added).
+ * An event row names its receiver as an instance slot (`target`); the reference publishes it to the client session that
+ * owns that instance (ManagedResourceSession.publish, ManagedResourceSession.java:64-71), and Copycat ships every
+ * client session its own ordered list of events.  cc_route_events is a stable grouping of a stream by owning client
+ * session: each session's events as one contiguous run, in the order the reference would have published them.  Host
+ * memory only, no engine; cc_route_events_device is the same call for a stream in HBM, byte for byte.
+ * Inputs:
+ *   - `in`: the stream's columns; n_events is a host number (after cc_merge_events* it is *total; after an apply the
+ *     host reads the 8-byte count).  in->count and in->capacity are not read.
+ *   - session_of_inst[slot]: the host's dense ordinal, in [0, n_sessions), of the client session that owns the instance
+ *     slot; id_of_inst[slot]: ManagedResourceSession.id() (both are what the host gave cc_instance_open or got from
+ *     cc_get_resource); n_inst entries each.  id_of_inst and out_instance are either both NULL or both set.
+ * Outputs:
+ *   - `out` holds the same rows ordered by session_of_inst[target] ascending; within a session the rows keep their
+ *     input order (log row first, then the state machine's publish order).  All six columns are copied unchanged: pos
+ *     is data here, never an index, so result rows (CC_EVSRC_RESULT) and close / timer rows (pos 0xFFFFFFFF) are
+ *     routed like every other row.  *out->count = n_events (when count is non-NULL); rows past n_events are not touched.
+ *   - out_instance[j] = id_of_inst[out->target[j]].
+ *   - `dir` lists only the sessions that received rows, ascending: dir->session[k] is the k-th such ordinal and
+ *     dir->start[k] the first row of its run; dir->start[*dir->count] = n_events.  *dir->count and *n_active take their
+ *     number.  Entries past these are not touched.  No array, neither an output nor the workspace, is sized by
+ *     n_sessions: a host whose closed slots should keep their rows maps them to a dead-letter ordinal of its own.
+ * Refusals: CC_ERR_INVALID with nothing written to out, out_instance or dir (all validation completes before the first
+ * store), for a target >= n_inst; a table entry >= n_sessions; n_sessions == 0 with n_events > 0; n_events >= 2^32; a
+ * NULL in / session_of_inst / out / dir / dir->start / dir->count / n_active, a NULL dir->session with capacity > 0, a
+ * NULL column with n_events > 0, one of id_of_inst / out_instance without the other; a column that lacks its natural
+ * alignment (4 bytes: pos, target, session_of_inst, dir->session, dir->start; 8 bytes: payload, count, id_of_inst,
+ * out_instance).  For a bad target or table entry cc_last_error names the lowest offending event, whatever order the
+ * checks ran in (the device keeps it with one atomicMin).
+ * Capacity, CC_ERR_CAPACITY with nothing written: out->capacity < n_events is answered before any work (*n_active is
+ * not written); dir->capacity < the number of active sessions is answered after the grouping, with *n_active set.
+ * *n_active is written by CC_OK and by the directory's CC_ERR_CAPACITY only.
+ * n_events == 0: CC_OK with *n_active = 0 once the arguments have passed; nothing else is stored (the device call makes
+ * no HIP call).  threads: worker threads (0 = hardware concurrency).
+ *
+ * cc_route_events_device:
+ *   - Every pointer inside d_in, d_out and d_dir, and d_session_of_inst, d_id_of_inst, d_out_instance are device
+ *     pointers; the structs themselves and n_active are host memory.  No engine is involved; the call runs on the
+ *     device that owns `stream` (the current device for the null stream).
+ *   - d_work: caller-owned device scratch, 16-byte aligned, of at least cc_route_events_device_bound(n_events,
+ *     n_sessions) bytes (host arithmetic, no HIP call: 16 B per event for the two (key, permutation) buffers and
+ *     about 0.26 B per event of tile counters).  A NULL, misaligned or smaller workspace is CC_ERR_INVALID.  Every
+ *     argument error above is answered before the first HIP call.
+ *   - A stable least-significant-digit radix ordering of (session ordinal, event number) is built in the workspace,
+ *     CC_ROUTE_DIGIT_BITS bits per round, ceil(bits(n_sessions - 1) / CC_ROUTE_DIGIT_BITS) rounds (none for one
+ *     session), a workgroup per CC_ROUTE_TILE_EVENTS events; then the directory is compacted and one gather moves the
+ *     rows.  Both constants are public so that tests can straddle them.
+ *   - The call waits on the host exactly once, at the end, for the error word and the number of active sessions.  The
+ *     kernels that store to d_out / d_out_instance / d_dir read the error word and the directory capacity on the
+ *     device and store nothing when either refuses the call.  On return every output is complete.
+ *   - Inputs, outputs and the workspace must not overlap.
+ *   - Peer memory: the outputs may be any memory the device can store to, another GPU's peer-mapped HBM included.
+ *     That is not exercised by the tests: the test box has one GPU.
+ * Not covered: packing the routed stream (cc_evpack_* is specified for streams whose pos is non-decreasing; pack before
+ * routing, or ship the routed columns wide), and an engine-owned copy of the two tables (the host owns the session
+ * ordinals). */
+#define CC_ROUTE_DIGIT_BITS 8
+#define CC_ROUTE_TILE_EVENTS 4096
+typedef struct cc_route_dir {   /* the sessions that received something, ascending by session ordinal */
+  uint32_t* session;            /* [capacity]      session ordinal                                     */
+  uint32_t* start;              /* [capacity + 1]  first row of that session's run in the routed stream;
+                                                   start[*count] = n_events                            */
+  uint64_t  capacity;
+  uint64_t* count;              /* number of sessions with at least one row */
+} cc_route_dir;
+int  cc_route_events(const cc_events* in, uint64_t n_events, const uint32_t* session_of_inst,
+                     const uint64_t* id_of_inst, uint32_t n_inst, uint32_t n_sessions, uint32_t threads,
+                     const cc_events* out, uint64_t* out_instance, const cc_route_dir* dir, uint64_t* n_active);
+int  cc_route_events_device_bound(uint64_t n_events, uint32_t n_sessions, uint64_t* work_bytes);
+int  cc_route_events_device(const cc_events* d_in, uint64_t n_events, const uint32_t* d_session_of_inst,
+                            const uint64_t* d_id_of_inst, uint32_t n_inst, uint32_t n_sessions,
+                            const cc_events* d_out, uint64_t* d_out_instance, const cc_route_dir* d_dir,
+                            uint64_t* n_active, void* d_work, uint64_t work_bytes, void* stream);
+/* Measurement aid (scripts/route_rate.py), per calling thread, off by default, as cc_merge_events_device_timing:
+ * ms[0..CC_ROUTE_TIMING_SLOTS) = the device times in milliseconds of k_route_key, of k_route_count, the scan kernels
+ * and k_route_scatter summed over the rounds, of the directory kernels, and of k_route_gather, for this thread's last
+ * cc_route_events_device call made while enabled. */
+#define CC_ROUTE_TIMING_SLOTS 6
+int  cc_route_events_device_timing(int enable, float* ms);
+
 /* ---- the same decode on the GPU: wire bytes in, device columns out (copycat_amd/csrc/wire_plain.h, wire_gpu.hip) ----
  * These calls exist from this commit on, under the unchanged CC_ABI_VERSION 6 (symbols are only added).
  * A Copycat host holds the log's serialized entries, not columns.  cc_wire_decode_to_device takes the log segment
