@@ -294,6 +294,24 @@ class cc_route_dir(C.Structure):
     _fields_ = [("session", C.c_void_p), ("start", C.c_void_p), ("capacity", C.c_uint64), ("count", C.c_void_p)]
 
 
+class cc_snapshot_info_t(C.Structure):
+    """What a snapshot was taken from (cc_snapshot_info)."""
+    _fields_ = [("max_resources", C.c_uint32), ("max_instances", C.c_uint32), ("map_capacity", C.c_uint64),
+                ("coord_cap", C.c_uint32), ("flags", C.c_uint32), ("applied", C.c_uint64)]
+
+
+CC_SNAP_COORD, CC_SNAP_TTL, CC_SNAP_VALUE_RETAINED = 1, 2, 4  # cc_snapshot_info_t.flags
+
+SNAPSHOT_GROW_PROTOTYPES = {
+    # (h_buf, size, out)
+    "cc_snapshot_info": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    # (e, h_buf, size)
+    "cc_snapshot_restore_grow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    # (enable, ms[3])
+    "cc_snapshot_grow_timing": (C.c_int, [C.c_int, C.c_void_p]),
+}
+
+
 class cc_wire_control(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("row", "kind", "key", "a", "b")]
 

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 
-ENGINE_SRCS = ["engine.hip", "apply_batch.hip", "map_big.hip", "partition.hip", "partition_ext.hip", "apply_value.hip", "value_path.hip", "apply_map.hip", "apply_map_hot.hip", "apply_coord.hip", "topic_fanout.hip", "events.hip", "quorum.hip", "close.hip", "map_wide.hip", "live.hip", "manager.hip", "retained.hip", "host_path.hip", "prefix_scan.hip", "map_small.hip", "map_cv.hip", "map_clear.hip", "wire.cpp", "split.cpp", "pack.cpp", "unpack.hip", "respack.cpp", "respack.hip", "evpack.cpp", "evpack.hip", "wire_gpu.hip", "split_gpu.hip", "evmerge.cpp", "evmerge_gpu.hip", "pack_enc.hip", "unpack_res.hip", "route.cpp", "route_gpu.hip"]
+ENGINE_SRCS = ["engine.hip", "apply_batch.hip", "map_big.hip", "partition.hip", "partition_ext.hip", "apply_value.hip", "value_path.hip", "apply_map.hip", "apply_map_hot.hip", "apply_coord.hip", "topic_fanout.hip", "events.hip", "quorum.hip", "close.hip", "map_wide.hip", "live.hip", "manager.hip", "retained.hip", "host_path.hip", "prefix_scan.hip", "map_small.hip", "map_cv.hip", "map_clear.hip", "wire.cpp", "split.cpp", "pack.cpp", "unpack.hip", "respack.cpp", "respack.hip", "evpack.cpp", "evpack.hip", "wire_gpu.hip", "split_gpu.hip", "evmerge.cpp", "evmerge_gpu.hip", "pack_enc.hip", "unpack_res.hip", "route.cpp", "route_gpu.hip", "grow.hip"]
 ENGINE_HDRS = ["common.h", "engine_internal.h", "engine_state.h", "map_ops.h", "java_hashmap.h", "small_jhm.h", "jhm_tree.h", "big_jhm.h", "wire_plain.h", "pack_host.h", "pack_dev.h", "evmerge.h", "value_group.h", "route.h"]
 ENGINE_SO = os.path.join(HERE, "libcopycat_apply.so")
 WORKLOAD_SO = os.path.join(HERE, "libcopycat_workload.so")
@@ -35,7 +35,7 @@ def _run(cmd):
 
 # Units compiled with the compiler's kernel resource report: kept beside the object file (<unit>.resources.txt), and a
 # kernel of theirs that uses scratch fails the build (these kernels have no engine self-check in front of them).
-REPORT_SRCS = ("split_gpu.hip", "evmerge_gpu.hip", "pack_enc.hip", "unpack_res.hip", "route_gpu.hip")
+REPORT_SRCS = ("split_gpu.hip", "evmerge_gpu.hip", "pack_enc.hip", "unpack_res.hip", "route_gpu.hip", "grow.hip")
 
 
 def _compile_unit(hipcc, flags, src, obj):

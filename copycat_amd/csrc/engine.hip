@@ -216,6 +216,35 @@ static bool is_coord(uint32_t type) {
 extern "C" int cc_abi_version(void) { return CC_ABI_VERSION; }
 extern "C" const char* cc_last_error(void) { return g_err.c_str(); }
 
+// The map state of an engine that holds no map: an empty table (word 0 = empty entry), no compacted key, every
+// capacity level unreached.  At creation, and when a snapshot without maps is restored into an engine with maps.
+static hipError_t maps_zero(cc_engine* e) {
+  hipError_t he;
+  if ((he = hipMemset(e->d_tbl_key, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_tbl_val, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_tbl_word, 0, sizeof(uint32_t) * e->map_entries)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_tbl_ci, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_tbl_ins, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_hot_n, 0, sizeof(uint32_t))) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_mw_peak, 0, sizeof(uint32_t) * e->cfg.max_resources)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_mw_drop, 0, sizeof(uint64_t) * e->cfg.max_resources)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_mw_cgen, 0, sizeof(uint64_t) * e->cfg.max_resources)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_cset, 0, sizeof(CsetEnt) * (e->cset_mask + 1))) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_cset_full, 0, sizeof(uint32_t))) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_tbl_claim, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_tbl_ep, 0, e->map_entries)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_lvl_at, 0xFF, sizeof(unsigned long long) * kLvlSlots * e->cfg.max_resources)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_msize, 0, sizeof(uint32_t) * e->cfg.max_resources)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_mpcap, 0, sizeof(uint32_t) * e->cfg.max_resources)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_msm, 0, sizeof(SmallMap) * e->cfg.max_resources)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_mbig, 0, sizeof(BigMap) * kBigSlots)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_msmall, 0, e->cfg.max_resources)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_msm_left, 0, 3ull * e->cfg.max_resources)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_sm_ctl, 0, sizeof(uint32_t) * 4)) != hipSuccess) return he;
+  if ((he = hipMemset(e->d_tbl_dl, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return he;
+  return hipSuccess;
+}
+
 extern "C" int cc_engine_create(const cc_config* cfg, cc_engine** out) {
   if (!cfg || !out) return set_err(CC_ERR_INVALID, "null config");
   if (cfg->max_resources == 0 || cfg->max_resources > (uint32_t)kMaxSb << kSbShift)
@@ -379,31 +408,7 @@ extern "C" int cc_engine_create(const cc_config* cfg, cc_engine** out) {
   // (never read before an instance is opened / an entry is bound, but snapshot sections: no heap leftovers in them)
   if ((he = hipMemset(e->d_inst_id, 0, sizeof(uint64_t) * cfg->max_instances)) != hipSuccess) return fail("memset", he);
   e->sb_kind.assign(e->sb, 0);
-  if (e->map_bits) {  // word 0 = empty entry
-    if ((he = hipMemset(e->d_tbl_key, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_tbl_val, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_tbl_word, 0, sizeof(uint32_t) * e->map_entries)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_tbl_ci, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_tbl_ins, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_hot_n, 0, sizeof(uint32_t))) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_mw_peak, 0, sizeof(uint32_t) * cfg->max_resources)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_mw_drop, 0, sizeof(uint64_t) * cfg->max_resources)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_mw_cgen, 0, sizeof(uint64_t) * cfg->max_resources)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_cset, 0, sizeof(CsetEnt) * (e->cset_mask + 1))) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_cset_full, 0, sizeof(uint32_t))) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_tbl_claim, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_tbl_ep, 0, e->map_entries)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_lvl_at, 0xFF, sizeof(unsigned long long) * kLvlSlots * cfg->max_resources)) != hipSuccess)
-      return fail("memset", he);
-    if ((he = hipMemset(e->d_msize, 0, sizeof(uint32_t) * cfg->max_resources)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_mpcap, 0, sizeof(uint32_t) * cfg->max_resources)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_msm, 0, sizeof(SmallMap) * cfg->max_resources)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_mbig, 0, sizeof(BigMap) * kBigSlots)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_msmall, 0, cfg->max_resources)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_msm_left, 0, 3ull * cfg->max_resources)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_sm_ctl, 0, sizeof(uint32_t) * 4)) != hipSuccess) return fail("memset", he);
-    if ((he = hipMemset(e->d_tbl_dl, 0, sizeof(uint64_t) * e->map_entries)) != hipSuccess) return fail("memset", he);
-  }
+  if (e->map_bits && (he = maps_zero(e)) != hipSuccess) return fail("memset", he);
   if ((he = hipDeviceSynchronize()) != hipSuccess) return fail("sync", he);
   // the stable rankings of k_part_scatter / k_apply_value need same-address LDS atomics of one wave
   // instruction to resolve in lane order: verify on this device before trusting any result
@@ -1526,14 +1531,19 @@ struct SnapHdr {
   uint64_t applied;
   uint32_t coord_cap, pad;
 };
+// The sections whose size follows map_capacity or coord_cap: cc_snapshot_restore_grow migrates them (grow.hip).
+enum : uint8_t { kSecPlain = 0, kSecKey, kSecWord, kSecVal, kSecCi, kSecIns, kSecDl, kSecClaim, kSecCset, kSecCoord, kSecKinds };
 struct Section {
   void* dev;
   void* host;
   uint64_t bytes;
+  uint8_t kind = kSecPlain;
 };
 }  // namespace
 
-static std::vector<Section> snap_sections(cc_engine* e) {
+// The sections of a snapshot of this engine, had it `map_bits` region bits (0: no maps) and coordination blocks of
+// `coord_cap` entries: the engine's own arrays, the sizes of that configuration.
+static std::vector<Section> snap_sections(cc_engine* e, uint32_t map_bits, uint32_t coord_cap) {
   const uint64_t slots = (uint64_t)e->sb << kSbShift, mi = e->cfg.max_instances, mr = e->cfg.max_resources;
   std::vector<Section> v = {
       {nullptr, e->res_type.data(), slots},
@@ -1554,20 +1564,20 @@ static std::vector<Section> snap_sections(cc_engine* e) {
       {nullptr, e->res_zombie.data(), slots},
   };
   if (e->d_val_live) v.push_back({e->d_val_live, nullptr, 8 * slots});
-  if (e->map_bits) {
-    const uint64_t n = e->map_entries;
-    v.push_back({e->d_tbl_key, nullptr, 8 * n});
-    v.push_back({e->d_tbl_word, nullptr, 4 * n});
-    v.push_back({e->d_tbl_val, nullptr, 8 * n});
-    v.push_back({e->d_tbl_ci, nullptr, 8 * n});
-    v.push_back({e->d_tbl_ins, nullptr, 8 * n});
-    v.push_back({e->d_tbl_dl, nullptr, 8 * n});
+  if (map_bits) {
+    const uint64_t n = (uint64_t)kMapRegion << map_bits;
+    v.push_back({e->d_tbl_key, nullptr, 8 * n, kSecKey});
+    v.push_back({e->d_tbl_word, nullptr, 4 * n, kSecWord});
+    v.push_back({e->d_tbl_val, nullptr, 8 * n, kSecVal});
+    v.push_back({e->d_tbl_ci, nullptr, 8 * n, kSecCi});
+    v.push_back({e->d_tbl_ins, nullptr, 8 * n, kSecIns});
+    v.push_back({e->d_tbl_dl, nullptr, 8 * n, kSecDl});
     v.push_back({e->d_mw_peak, nullptr, 4 * mr});
     v.push_back({e->d_mw_drop, nullptr, 8 * mr});
     v.push_back({e->d_mw_cgen, nullptr, 8 * mr});
-    v.push_back({e->d_cset, nullptr, sizeof(CsetEnt) * (e->cset_mask + 1)});
+    v.push_back({e->d_cset, nullptr, sizeof(CsetEnt) * std::max<uint64_t>(1u << 16, n), kSecCset});
     v.push_back({e->d_cset_full, nullptr, 4});
-    v.push_back({e->d_tbl_claim, nullptr, 8 * n});
+    v.push_back({e->d_tbl_claim, nullptr, 8 * n, kSecClaim});
     v.push_back({e->d_lvl_at, nullptr, 8ull * kLvlSlots * mr});
     v.push_back({e->d_msize, nullptr, 4 * mr});
     v.push_back({e->d_mpcap, nullptr, 4 * mr});
@@ -1575,9 +1585,10 @@ static std::vector<Section> snap_sections(cc_engine* e) {
     v.push_back({e->d_mbig, nullptr, sizeof(BigMap) * kBigSlots});
     v.push_back({e->d_msmall, nullptr, mr});
   }
-  if (e->coord_on) v.push_back({e->d_coord, nullptr, coord_block(e->coord_cap) * slots});
+  if (e->coord_on) v.push_back({e->d_coord, nullptr, coord_block(coord_cap) * slots, kSecCoord});
   return v;
 }
+static std::vector<Section> snap_sections(cc_engine* e) { return snap_sections(e, e->map_bits, e->coord_cap); }
 
 // ---- the prefix apply's checkpoint (host_path.hip cc_apply_batch_host_prefix) -------------------------------------
 // The device sections of a snapshot (the state every batch apply may write), the applied index and the leak log's
@@ -1756,14 +1767,71 @@ static bool snap_room(const uint8_t* p, const uint8_t* end, uint64_t count, uint
   return p <= end && count <= (uint64_t)(end - p) / rec;
 }
 
-extern "C" int cc_snapshot_restore(cc_engine* e, const void* h_buf, uint64_t size) {
-  if (!e || !h_buf || size < sizeof(SnapHdr)) return set_err(CC_ERR_INVALID, "snapshot too small");
-  SnapHdr h;
+// A snapshot's header, its magic and ABI checked.
+static int snap_header(const void* h_buf, uint64_t size, SnapHdr& h) {
+  if (!h_buf || size < sizeof(SnapHdr)) return set_err(CC_ERR_INVALID, "snapshot too small");
   memcpy(&h, h_buf, sizeof h);
   if (h.magic != kSnapMagic || h.abi != CC_ABI_VERSION) return set_err(CC_ERR_INVALID, "not a snapshot of this engine ABI");
-  if (h.max_resources != e->cfg.max_resources || h.max_instances != e->cfg.max_instances || h.map_bits != e->map_bits ||
-      h.sb != e->sb || h.coord_cap != e->coord_cap)
+  return CC_OK;
+}
+
+extern "C" int cc_snapshot_info(const void* h_buf, uint64_t size, cc_snapshot_info_t* out) {
+  if (!out) return set_err(CC_ERR_INVALID, "null snapshot info");
+  SnapHdr h;
+  const int rc = snap_header(h_buf, size, h);
+  if (rc) return rc;
+  if ((1ull << std::min(h.map_bits, 31u)) > (uint64_t)kMaxMapSb || h.coord_cap < kCoordCapDefault || h.coord_cap > kCoordCapMax ||
+      (h.coord_cap & (h.coord_cap - 1)))
+    return set_err(CC_ERR_INVALID, "snapshot header: no engine has this map table or coord_cap");
+  *out = cc_snapshot_info_t{};
+  out->max_resources = h.max_resources;
+  out->max_instances = h.max_instances;
+  out->map_capacity = h.map_bits ? ((uint64_t)kMapRegion << h.map_bits) / 2 : 0;
+  out->coord_cap = h.coord_cap;
+  out->flags = h.flags & (CC_SNAP_COORD | CC_SNAP_TTL | CC_SNAP_VALUE_RETAINED);
+  out->applied = h.applied;
+  return CC_OK;
+}
+
+// The snapshot's sections that change shape, staged on the device (each as it was saved) and moved into the engine's
+// arrays by grow.hip's kernels; `tmp[kind]` is null for a section that kept its size and was copied in place.
+static int snap_migrate(cc_engine* e, const SnapHdr& h, void* const* tmp) {
+  hipStream_t st = e->own_stream;
+  if (tmp[kSecWord]) {
+    const TblCols old{(uint64_t*)tmp[kSecKey], (uint32_t*)tmp[kSecWord], (uint64_t*)tmp[kSecVal], (uint64_t*)tmp[kSecCi],
+                      (uint64_t*)tmp[kSecIns], (uint64_t*)tmp[kSecDl], (uint64_t*)tmp[kSecClaim]};
+    const TblCols dst{e->d_tbl_key, e->d_tbl_word, e->d_tbl_val, e->d_tbl_ci, e->d_tbl_ins, e->d_tbl_dl, (uint64_t*)e->d_tbl_claim};
+    if (launch_grow_table(old, h.map_bits, dst, e->map_bits, st)) return set_err(CC_ERR_HIP, "grow table launch", hipGetLastError());
+  }
+  if (tmp[kSecCset]) {  // (after the plain sections: the insert reads the restored generations, ORs the restored full flag)
+    HIPCHECK(hipMemsetAsync(e->d_cset, 0, sizeof(CsetEnt) * (e->cset_mask + 1), st));
+    const uint64_t old_n = std::max<uint64_t>(1u << 16, (uint64_t)kMapRegion << h.map_bits);
+    if (launch_grow_cset((const CsetEnt*)tmp[kSecCset], old_n, e->d_cset, e->cset_mask, e->d_cset_full, e->d_mw_cgen,
+                         e->cfg.max_resources, st))
+      return set_err(CC_ERR_HIP, "grow cset launch", hipGetLastError());
+  }
+  if (tmp[kSecCoord]) {
+    const uint64_t slots = (uint64_t)e->sb << kSbShift;
+    HIPCHECK(hipMemsetAsync(e->d_coord, 0, coord_block(e->coord_cap) * slots, st));
+    if (launch_grow_coord((const uint8_t*)tmp[kSecCoord], h.coord_cap, e->d_coord, e->coord_cap, e->d_res_type, slots, st))
+      return set_err(CC_ERR_HIP, "grow coord launch", hipGetLastError());
+  }
+  HIPCHECK(hipStreamSynchronize(st));
+  return CC_OK;
+}
+
+// cc_snapshot_restore (grow = false: the snapshot's geometry is the engine's) and cc_snapshot_restore_grow.
+static int snap_restore(cc_engine* e, const void* h_buf, uint64_t size, bool grow) {
+  if (!e) return set_err(CC_ERR_INVALID, "null engine");
+  SnapHdr h;
+  int rc = snap_header(h_buf, size, h);
+  if (rc) return rc;
+  if (h.max_resources != e->cfg.max_resources || h.max_instances != e->cfg.max_instances || h.sb != e->sb ||
+      (!grow && (h.map_bits != e->map_bits || h.coord_cap != e->coord_cap)))
     return set_err(CC_ERR_INVALID, "snapshot configuration (max_resources/max_instances/map_capacity/coord_cap) differs");
+  if (h.map_bits > e->map_bits || h.coord_cap > e->coord_cap || h.coord_cap < kCoordCapDefault || (h.coord_cap & (h.coord_cap - 1)))
+    return set_err(CC_ERR_INVALID, "snapshot map_capacity or coord_cap is larger than the engine's (or no engine's)");
+  grow = h.map_bits != e->map_bits || h.coord_cap != e->coord_cap;  // (nothing grows: cc_snapshot_restore's path)
   if (((h.flags & kSnapRetained) != 0) != (e->d_val_live != nullptr))  // the section lists would differ
     return set_err(CC_ERR_INVALID, "snapshot and engine differ in CC_CFG_VALUE_RETAINED");
   if (e->coord_on && !(h.flags & 1u))  // the engine's coordination blocks have no section to come from
@@ -1772,8 +1840,8 @@ extern "C" int cc_snapshot_restore(cc_engine* e, const void* h_buf, uint64_t siz
   const uint8_t* const end = (const uint8_t*)h_buf + size;
   // 1. validate the whole buffer before any engine state changes: a rejected snapshot leaves the engine as it was
   std::vector<uint64_t> sizes;
-  for (const Section& x : snap_sections(e)) sizes.push_back(x.bytes);
-  if ((h.flags & 1u) && !e->coord_on) sizes.push_back(coord_block(e->coord_cap) * ((uint64_t)e->sb << kSbShift));
+  for (const Section& x : snap_sections(e, h.map_bits, h.coord_cap)) sizes.push_back(x.bytes);
+  if ((h.flags & 1u) && !e->coord_on) sizes.push_back(coord_block(h.coord_cap) * ((uint64_t)e->sb << kSbShift));
   const uint8_t* p = base;
   for (uint64_t want : sizes) {
     uint64_t b = 0;
@@ -1813,16 +1881,55 @@ extern "C" int cc_snapshot_restore(cc_engine* e, const void* h_buf, uint64_t siz
   p += 8;
   if (!snap_room(p, end, nl, 16)) return set_err(CC_ERR_INVALID, "snapshot truncated (leak lists)");
   // 2. apply
-  int rc = quiesce(e);
-  if (rc) return rc;
+  if ((rc = quiesce(e))) return rc;
   if ((h.flags & 1u) && (rc = ensure_ext(e, true))) return rc;
+  // a section whose size differs from the engine's is staged on the device (all staging is allocated before the first
+  // store into engine state) and migrated below, once the plain sections are in place
+  void* tmp[kSecKinds] = {};
+  auto drop_tmp = [&tmp] {
+    for (void*& t : tmp) {
+      if (t) (void)hipFree(t);
+      t = nullptr;
+    }
+  };
+  const std::vector<Section> secs = snap_sections(e, h.map_bits, h.coord_cap);
+  if (grow) {
+    uint64_t own[kSecKinds] = {};
+    for (const Section& x : snap_sections(e)) own[x.kind] = x.bytes;
+    for (const Section& x : secs) {
+      if (x.kind == kSecPlain || x.bytes == own[x.kind]) continue;
+      const hipError_t he = hipMalloc(&tmp[x.kind], x.bytes);
+      if (he != hipSuccess) {
+        tmp[x.kind] = nullptr;
+        drop_tmp();
+        return set_err(CC_ERR_HIP, "hipMalloc (snapshot staging)", he);
+      }
+    }
+  }
   e->ttl_live = (h.flags & 2u) != 0;
   p = base;
-  for (const Section& x : snap_sections(e)) {
+  for (const Section& x : secs) {
     p += 8;
-    if (x.dev) HIPCHECK(hipMemcpy(x.dev, p, x.bytes, hipMemcpyHostToDevice));
+    hipError_t he = hipSuccess;
+    if (x.dev) he = hipMemcpy(tmp[x.kind] ? tmp[x.kind] : x.dev, p, x.bytes, hipMemcpyHostToDevice);
     else memcpy(x.host, p, x.bytes);
+    if (he != hipSuccess) {
+      drop_tmp();
+      return set_err(CC_ERR_HIP, "hipMemcpy (snapshot section)", he);
+    }
     p += x.bytes;
+  }
+  if (grow) {
+    if (!h.map_bits && e->map_bits) {  // a snapshot without maps: the engine's table starts empty
+      const hipError_t he = maps_zero(e);
+      if (he != hipSuccess) {
+        drop_tmp();
+        return set_err(CC_ERR_HIP, "memset", he);
+      }
+    }
+    rc = snap_migrate(e, h, tmp);
+    drop_tmp();
+    if (rc) return rc;
   }
   p = hh_at + nh * 16;  // (the sessions table and handle hashes were parsed above)
   memcpy(&e->gtimer_seq, p + 8, 8);
@@ -1908,6 +2015,9 @@ extern "C" int cc_snapshot_restore(cc_engine* e, const void* h_buf, uint64_t siz
   HIPCHECK(hipMemset(e->d_err, 0, sizeof(uint32_t)));
   return CC_OK;
 }
+
+extern "C" int cc_snapshot_restore(cc_engine* e, const void* h_buf, uint64_t size) { return snap_restore(e, h_buf, size, false); }
+extern "C" int cc_snapshot_restore_grow(cc_engine* e, const void* h_buf, uint64_t size) { return snap_restore(e, h_buf, size, true); }
 
 extern "C" int cc_profile_enable(cc_engine* e, int on) {
   if (!e) return CC_ERR_INVALID;

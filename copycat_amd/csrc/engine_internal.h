@@ -1009,4 +1009,24 @@ struct WireChunkIn {
 int wire_chunk_decode(cc_engine* e, const WireChunkIn& in, hipStream_t st, uint64_t* apply, bool* end, int* end_rc,
                       cc_wire_control* ctl, uint64_t* bad_row);
 
+// ---- cc_snapshot_restore_grow's migrations (grow.hip): a snapshot's sections that change shape, uploaded to temporary
+//      buffers (`old`), into the arrays of an engine with more room.  Launches only; the caller waits on `st`.
+struct TblCols {  // the map table's seven columns
+  uint64_t* key;
+  uint32_t* word;
+  uint64_t* val;
+  uint64_t* ci;
+  uint64_t* ins;
+  uint64_t* dl;
+  uint64_t* claim;
+};
+// old region r's bound entries into its 2^(new_bits - old_bits) children (old_bits < new_bits)
+int launch_grow_table(const TblCols& old, uint32_t old_bits, const TblCols& dst, uint32_t new_bits, hipStream_t st);
+// the occupied entries of the current generation into the zeroed `dst` (cgen: the restored d_mw_cgen, max_resources words)
+int launch_grow_cset(const CsetEnt* old, uint64_t old_n, CsetEnt* dst, uint64_t new_mask, uint32_t* full, const uint64_t* cgen,
+                     uint32_t max_resources, hipStream_t st);
+// blocks of old_cap entries into the zeroed blocks of new_cap entries (res_type: the restored d_res_type)
+int launch_grow_coord(const uint8_t* old, uint32_t old_cap, uint8_t* dst, uint32_t new_cap, const uint8_t* res_type,
+                      uint64_t slots, hipStream_t st);
+
 }  // namespace cc

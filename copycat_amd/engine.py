@@ -156,6 +156,7 @@ def lib():
             "cc_wire_packed_timeline": (i32, [P, u64, P, P]),
         }
         sig.update(abi.PACK_DEVICE_PROTOTYPES)
+        sig.update(abi.SNAPSHOT_GROW_PROTOTYPES)
         # the value-only apply's group / segment arithmetic (host calls; a library picked through CC_ENGINE_SO for an
         # A/B against an earlier commit may predate them)
         value_group = {
@@ -268,6 +269,9 @@ class Engine:
         self.max_instances = max_instances
         self.device = device
         self.L = L
+        self._config = dict(max_resources=max_resources, max_instances=max_instances, max_batch=max_batch, device=device,
+                            flags=flags, sub_batch=sub_batch, max_events=max_events, map_capacity=map_capacity,
+                            coord_cap=coord_cap)
 
     def close(self):
         if self.h:
@@ -795,10 +799,38 @@ class Engine:
         _check(self.L.cc_snapshot_save(self.h, _np(buf), n.value))
         return buf.tobytes()
 
-    def restore(self, snap: bytes):
-        """Load a snapshot into this engine (same max_resources / max_instances / map_capacity)."""
+    def restore(self, snap: bytes, grow=False):
+        """Load a snapshot into this engine: one of the same max_resources / max_instances / map_capacity / coord_cap
+        (cc_snapshot_restore), or with grow=True one whose map_capacity and coord_cap are no larger than this engine's
+        (cc_snapshot_restore_grow)."""
         buf = np.frombuffer(snap, np.uint8).copy()
-        _check(self.L.cc_snapshot_restore(self.h, _np(buf), len(buf)))
+        fn = self.L.cc_snapshot_restore_grow if grow else self.L.cc_snapshot_restore
+        _check(fn(self.h, _np(buf), len(buf)))
+
+    @staticmethod
+    def snapshot_info(snap: bytes) -> dict:
+        """What a snapshot was taken from (cc_snapshot_info: the header only, no engine and no device)."""
+        buf = np.frombuffer(snap, np.uint8).copy()
+        info = abi.cc_snapshot_info_t()
+        _check(lib().cc_snapshot_info(_np(buf), len(buf), C.byref(info)))
+        return {name: getattr(info, name) for name, _ in abi.cc_snapshot_info_t._fields_}
+
+    def grown(self, coord_cap=None, map_capacity=None):
+        """A new engine of this engine's configuration with a larger coord_cap and / or map_capacity, holding this
+        engine's state (snapshot, then restore with grow=True).  This engine stays as it is; close it when done."""
+        cfg = dict(self._config)
+        if coord_cap is not None:
+            cfg["coord_cap"] = coord_cap
+        if map_capacity is not None:
+            cfg["map_capacity"] = map_capacity
+        snap = self.snapshot()
+        e = Engine(**cfg)
+        try:
+            e.restore(snap, grow=True)
+        except Exception:
+            e.close()
+            raise
+        return e
 
     def lock_state(self, slot, cap=1024):
         """(holder instance slot or -1, holder index, holder cleaned, [(waiter instance slot, index)])"""

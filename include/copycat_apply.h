@@ -406,10 +406,56 @@ int  cc_applied_index_async(cc_engine* e, uint64_t* d_out, void* stream);
 /* ---- snapshot / restore ---------------------------------------------------------------------------
  * Replaces recovery by full log replay (the reference replays Copycat's log, AbstractReplicaTest.java:82-84):
  * the engine's whole device state plus its host registry mirrors, as one host buffer.  Save syncs first;
- * restore needs an engine created with the same max_resources, max_instances and map_capacity. */
+ * cc_snapshot_restore needs an engine created with the same max_resources, max_instances, map_capacity (the same
+ * table: the same number of 2,048-entry regions) and coord_cap; cc_snapshot_restore_grow (below) takes an engine
+ * whose map_capacity and coord_cap are the same or larger. */
 int  cc_snapshot_size(cc_engine* e, uint64_t* bytes);
 int  cc_snapshot_save(cc_engine* e, void* h_buf, uint64_t cap);
 int  cc_snapshot_restore(cc_engine* e, const void* h_buf, uint64_t size);
+
+/* ---- restore into an engine with larger capacities --------------------------------------------------
+ * The engine's collections are fixed at creation (coord_cap entries per coordination block, map_capacity live map / set
+ * / multimap entries); the reference's are unbounded.  When a prefix apply (cc_apply_batch_host_prefix,
+ * cc_apply_batch_prefix) stops before a commit that a full block or table region cannot hold, the host saves a
+ * snapshot, reads what it was taken from (cc_snapshot_info), creates an engine with a larger coord_cap and / or
+ * map_capacity, restores into it with cc_snapshot_restore_grow and resumes at the stopped row: no commit fails that the
+ * reference would have applied.
+ *
+ * cc_snapshot_info reads the snapshot's header only: no engine, no HIP call.  map_capacity is the largest
+ * cc_config.map_capacity that gives the snapshot's table (table entries / 2; 0: no maps).  CC_ERR_INVALID on a NULL
+ * argument, a buffer shorter than the header, or a buffer that is no snapshot of this ABI.
+ *
+ * cc_snapshot_restore_grow accepts a snapshot whose max_resources, max_instances and CC_CFG_VALUE_RETAINED equal the
+ * engine's, with coord_cap <= the engine's and a map table no larger than the engine's.  A snapshot without maps
+ * restores into an engine with maps as an empty table; the reverse, and any shrink, is CC_ERR_INVALID.  Everything
+ * cc_snapshot_restore validates is validated the same way and before any engine state changes (a refused call leaves
+ * the engine as it was), and the staging memory is allocated before the first store into engine state.  When nothing
+ * grows the call is cc_snapshot_restore.
+ *
+ * Afterwards the engine behaves as the snapshot's engine would have, with more room: every cc_read_* reader,
+ * cc_retained_bitmap and cc_applied_index report what the source engine reported, and every later apply gives the
+ * results, events and state the reference gives.  No per-map model moves (sizes, HashMap capacity levels, the small and
+ * big models, the peak and drop counters, generations, the compacted-key set's membership).  Positions inside the map
+ * table are no part of the contract.  A snapshot saved from the grown engine is an ordinary snapshot of the new
+ * configuration (cc_snapshot_restore takes it).  The sections that change shape (the map table's columns, the
+ * compacted-key set, the coordination blocks) are migrated on the device (grow.hip).
+ *
+ * cc_snapshot_grow_timing(enable, ms): diagnostics.  Copies the calling thread's last cc_snapshot_restore_grow's
+ * kernel times to ms[0..2] (milliseconds: table, compacted-key set, coordination blocks; 0 for a kernel that did not
+ * run; ms may be NULL), then switches the timing on or off for that thread's next calls (on: the call waits after each
+ * kernel).  These calls exist from this commit on, under the unchanged CC_ABI_VERSION 6 (symbols are only added). */
+#define CC_SNAP_COORD           1u  /* cc_snapshot_info_t.flags: the snapshot holds coordination blocks */
+#define CC_SNAP_TTL             2u  /*   its maps were in TTL mode */
+#define CC_SNAP_VALUE_RETAINED  4u  /*   its engine was created with CC_CFG_VALUE_RETAINED */
+typedef struct cc_snapshot_info_t {   /* what a snapshot was taken from */
+  uint32_t max_resources, max_instances;
+  uint64_t map_capacity;
+  uint32_t coord_cap, flags;
+  uint64_t applied;
+} cc_snapshot_info_t;
+int  cc_snapshot_info(const void* h_buf, uint64_t size, cc_snapshot_info_t* out);
+int  cc_snapshot_restore_grow(cc_engine* e, const void* h_buf, uint64_t size);
+int  cc_snapshot_grow_timing(int enable, float* ms);
 
 /* ---- state readback for parity checks ------------------------------------------------------------ */
 /* AtomicValueState {value, current != null} for slots [first, first+count) (AtomicValueState.java:34-35) */
@@ -598,7 +644,8 @@ int  cc_wire_decode(cc_engine* e, const cc_wire_codec* codec, cc_wire_interner* 
  * list / member set / queue is not applied: the call returns CC_ERR_CAPACITY with *h_applied = that row, the engine
  * state is exactly the state after rows [0, *h_applied), the events of those rows are in h_events, and rows from
  * *h_applied on are not applied (their result rows keep what the caller put there).  The host resumes at that row
- * (e.g. on an engine with a larger coord_cap restored from a snapshot, or treating the commit as failed).  On success
+ * (on an engine with a larger coord_cap or map_capacity restored from a snapshot, cc_snapshot_restore_grow above, or
+ * treating the commit as failed).  On success
  * *h_applied = n.  Round 6: the same holds for a row whose map / set / multimap entry a full table region cannot
  * hold, and for a row whose events do not fit h_events' capacity (or max_events): the engine takes a device
  * checkpoint before each part of the batch and, when a part fails on one of those capacities, restores it and
