@@ -57,15 +57,7 @@ __global__ __launch_bounds__(256) void k_quorum(const uint64_t* __restrict__ mat
     o.y = (n1 >= ts.y && n1 > ci.y) ? n1 : ci.y;
     reinterpret_cast<u64x2*>(cout)[p] = o;
   }
-  // odd tail
-  if (blockIdx.x == 0 && threadIdx.x == 0 && (groups & 1)) {
-    const uint64_t g = groups - 1;
-    uint64_t m[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) m[r] = match[(uint64_t)r * groups + g];
-    const uint64_t n = kth_largest<R>(m, q);
-    cout[g] = (n >= term_start[g] && n > cin[g]) ? n : cin[g];
-  }
+  // (no odd tail: cc_quorum_commit launches this kernel for an even `groups` only; k_quorum_generic takes the rest)
 }
 
 // generic replica count (unaligned / unusual R): one group per thread, R <= 16

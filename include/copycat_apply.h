@@ -253,7 +253,23 @@ typedef struct cc_config {
 /* ---- one batch of committed entries, SoA, log order ------------------------------------------------
  * Row i is InstanceCommand/InstanceQuery{instance, op} of log entry index[i]
  * (InstanceOperation.java:59-69; ResourceManagerCommit.index/time ResourceManagerCommit.java:54-66).
- * Columns an op does not use may hold anything; pointers of columns no op in the batch uses may be NULL. */
+ * Columns an op does not use may hold anything; pointers of columns no op in the batch uses may be NULL.
+ * The columns each op reads (`a` implies tag a of the flags byte, `b` tag b, `key` the key tag; an unused tag field may
+ * hold any bits, the result-only tags 5..7 and an unregistered HANDLE key tag included):
+ *
+ *   key a b aux | MAP_REPLACEIFPRESENT
+ *   key a aux   | MAP_PUT, MAP_PUTIFABSENT, MAP_REPLACE, MMAP_PUT, GROUP_SCHEDULE
+ *   key a       | MAP_GETORDEFAULT, MAP_REMOVEIFPRESENT, MMAP_CONTAINSENTRY, MMAP_REMOVE, GROUP_EXECUTE
+ *   key aux     | SET_ADD
+ *   key         | MAP_CONTAINSKEY, MAP_GET, MAP_REMOVE, MMAP_CONTAINSKEY, MMAP_GET, MMAP_SIZE, SET_CONTAINS, SET_REMOVE
+ *   a b         | VALUE_CAS
+ *   a           | VALUE_SET, VALUE_GETANDSET, MAP_CONTAINSVALUE, MMAP_CONTAINSVALUE, MMAP_REMOVEVALUE, QUEUE_CONTAINS,
+ *                 QUEUE_ADD, QUEUE_OFFER, QUEUE_REMOVE, TOPIC_PUBLISH, BUS_JOIN, BUS_REGISTER, BUS_UNREGISTER
+ *   aux         | LOCK_LOCK
+ *
+ * Every other op byte reads nothing; index, time, inst and op are always read.  The op decides, not the resource it
+ * lands on: a MAP_PUT on a lock is an unknown operation whatever its columns hold.  (tests/abi_cases.py USED is the
+ * same table; tests/test_gpu_dont_care.py and tests/test_gpu_op_matrix.py hold the engine to it.) */
 typedef struct cc_batch {
   const uint64_t* index;  /* log index (Commit.index())                                         */
   const uint64_t* time;   /* log time, ms (Commit.time()); drives TTL / timeout timers           */
